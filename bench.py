@@ -16,7 +16,14 @@ torch, see aa-admm_amd/rdzv.py). Elastic configs partition ONE mesh over the ran
 solve and all residual/Anderson partials all-reduced on RCCL over xGMI; strong scaling);
 --partition none runs independent replicas (weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--iters 100] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--iters 100] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (`roofline`, `time_to_eps`,
+`secondary`, `cpu_baseline` are null). --full adds every other leg to the same line: the
+instrumented roofline pass and the read ceiling, the run-to-epsilon leg, the C3 secondary of the C4
+line and the reference CPU baseline (each with its own switch: --no-cpu-baseline, --eps-steps 0,
+--geom-eps-solves 0, --no-secondary). --dump-outputs DIR writes what the last timed step returned
+to its caller as DIR/<name>.npy (float64).
 """
 from __future__ import annotations
 
@@ -47,6 +54,13 @@ def parse():
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--iters", type=int, default=100)
     p.add_argument("--nx", type=int, default=112)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the legs that need runs of their own: the instrumented "
+                        "roofline pass and the read ceiling, the run-to-epsilon leg, the C3 secondary of the C4 line "
+                        "and the reference CPU baseline (off by default: a plain run only times the steps)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned to its caller as DIR/<name>.npy (float64): "
+                        "elastic x, v, prim, comb; geometry x, comb (a seeded row sample of an array above 16 MB)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-iters", type=int, default=40)
     p.add_argument("--config", default="c4", choices=["c2", "c3", "c4", "c5"],
@@ -85,7 +99,10 @@ def parse():
     p.add_argument("--lq-stats", action="store_true",
                    help="c4: count the local step's L-BFGS iterations per element and its work-queue trips over "
                         "the timed steps (AA_LQ_STATS=1; atomics in the kernel, so not for the timed number)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def free_port():
@@ -267,6 +284,22 @@ def geom_cpu_baseline(args):
                       f"(setup excluded, as ALMGeometrySolver.h:194-195)"}
 
 
+DUMP_MAX_BYTES = 16 << 20   # per array of --dump-outputs (at most 4 arrays: 64 MB in all)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float64; of an array above DUMP_MAX_BYTES
+    a fixed sample of rows (sorted indices drawn once from a seeded generator, the same in every run
+    of the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64)
+        if a.nbytes > DUMP_MAX_BYTES:
+            rows = max(1, DUMP_MAX_BYTES // max(1, a.nbytes // len(a)))
+            a = a[np.sort(np.random.default_rng(20191015).choice(len(a), rows, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 MALL_BYTES = 256e6   # MI355X Infinity Cache: working sets below it are flagged cache-resident
 
 
@@ -323,14 +356,16 @@ def geom_line(args, world, rank, local, group):
     barrier(group, ctx)
     elapsed = time.perf_counter() - t0
     elapsed_max = allreduce(group, elapsed, "max")
+    if args.dump_outputs and rank == 0:   # the last timed solve: get_solution() and function_values_
+        dump_outputs(args.dump_outputs, {"x": g.solution(), "comb": h["comb"]})
     # replicas: independent copies (weak scaling); partitioned: one problem (strong scaling)
     acc_all = float(acc) if comm is not None else allreduce(group, float(acc), "sum")
     geps = geom_run_to_eps(g, sc, eps, args) if args.geom_eps_solves > 0 else None
     value = acc_all / elapsed_max
     roof, cpu, line = None, None, None
-    if comm is not None:
+    if comm is not None and args.full:
         g.bench_iterations(min(sc.iters, 50))
-    if rank == 0:
+    if rank == 0 and args.full:
         if comm is None:
             g.bench_iterations(min(sc.iters, 50))
         stats = {k: g.kernel_stats(k) for k in ("z", "rhs", "solve", "u", "aa")}
@@ -364,6 +399,7 @@ def geom_line(args, world, rank, local, group):
                                "bound": "latency/divergence (per-lane BVH traversal, 3xk Jacobi SVDs)",
                                "avg_launch_us": round(z["avg_ms"] * 1e3, 2), "constraints": ncon,
                                "ns_per_constraint": round(z["avg_ms"] * 1e6 / max(ncon, 1), 3)}
+    if rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             print(f"[bench] timing the reference CPU baseline ({args.config})", file=sys.stderr, flush=True)
             try:
@@ -620,7 +656,8 @@ def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
-    if args.rehearse > 1:   # a timing rehearsal is not a bench line: no baselines, no eps leg
+    # a plain run only times the steps; a timing rehearsal is not a bench line: no baselines, no eps leg
+    if not args.full or args.rehearse > 1:
         args.no_cpu_baseline, args.no_secondary, args.eps_steps, args.geom_eps_solves = True, True, 0, 0
     world, rank, local, group, report = dist_setup(args.gpus)
     if args.launch_check:
@@ -684,6 +721,8 @@ def main():
     barrier(group, ctx)
     elapsed = time.perf_counter() - t0
     elapsed_max = allreduce(group, elapsed, "max")
+    if args.dump_outputs and rank == 0:   # the last timed step: Solver::m_x, m_v and the rows save() writes
+        dump_outputs(args.dump_outputs, {"x": solver.x, "v": solver.v, "prim": h["prim"], "comb": h["comb"]})
     # replicas: every rank ran its own copy of the scene (weak scaling); partitioned: all ranks
     # ran ONE scene together (strong scaling), its iterations count once
     iters_all = float(iters_run) if comm is not None else allreduce(group, float(iters_run), "sum")
@@ -700,11 +739,11 @@ def main():
               "lane_busy_frac": round(its / max(1, 64 * st["trips"]), 4)}
     # roofline of the dominant kernel class, timed live with HIP events on the solver's stream
     # (separate instrumented pass of the same iteration loop, after the timed region; every
-    # rank of a partitioned run takes part -- the loop has collectives)
+    # rank of a partitioned run takes part -- the loop has collectives); --full only
     roof = None
-    if comm is not None:
+    if comm is not None and args.full:
         solver.bench_iterations(min(args.iters, 50))
-    if rank == 0:
+    if rank == 0 and args.full:
         if comm is None:
             solver.bench_iterations(min(args.iters, 50))
         names = ("local_z", "solve", "resid", "rhs", "aa") if sc.variant == 1 else \
@@ -757,7 +796,7 @@ def main():
     # at N > 1 as independent replicas (the partitioned geometry path is exercised by the tests)
     secondary = None
     if args.config == "c4" and not args.no_secondary:
-        a3 = argparse.Namespace(**{**vars(args), "config": "c3", "iters": 100, "nx": 112,
+        a3 = argparse.Namespace(**{**vars(args), "config": "c3", "iters": 100, "nx": 112, "dump_outputs": None,
                                    "partition": "none" if world > 1 else args.partition})
         try:
             secondary = geom_line(a3, world, rank, local, group)

@@ -19,6 +19,8 @@ import importlib
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from golden_io import save_npz  # noqa: E402
 gs = importlib.import_module("aa-admm_amd.geom_scenes")
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -51,7 +53,7 @@ def main():
         out[f"{key}__face_sizes"] = np.array([len(f) for f in F], np.int32)
         out[f"{key}__face_idx"] = np.array([v for f in F for v in f], np.int32)
         print(key, {k: v.shape for k, v in out.items() if k.startswith(key)})
-    np.savez_compressed(os.path.join(HERE, "quality_reports.npz"), **out)
+    save_npz(os.path.join(HERE, "quality_reports.npz"), out)
 
 
 if __name__ == "__main__":

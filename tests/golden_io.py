@@ -13,6 +13,40 @@ if REPO not in sys.path:
 scenes = importlib.import_module("aa-admm_amd.scenes")
 geom_scenes = importlib.import_module("aa-admm_amd.geom_scenes")
 GOLDEN = os.path.join(REPO, "tests", "golden")
+MAX_FILE_BYTES = 1 << 20   # no committed file is larger
+
+
+def _parts_path(path):
+    return os.path.join(os.path.dirname(path), "parts", os.path.basename(path))
+
+
+def save_npz(path, d):
+    """np.savez_compressed(path, **d) for a fixture that may not fit one committed file: while
+    the file is above MAX_FILE_BYTES its largest array moves to parts/<file name> beside it
+    (load_npz merges the two)."""
+    main, rest = dict(d), {}
+    np.savez_compressed(path, **main)
+    for k in sorted(d, key=lambda k: -np.asarray(d[k]).nbytes):
+        if os.path.getsize(path) <= MAX_FILE_BYTES:
+            break
+        rest[k] = main.pop(k)
+        np.savez_compressed(path, **main)
+    if rest:
+        os.makedirs(os.path.dirname(_parts_path(path)), exist_ok=True)
+        np.savez_compressed(_parts_path(path), **rest)
+        assert os.path.getsize(_parts_path(path)) <= MAX_FILE_BYTES, "fixture needs more than two files"
+
+
+def load_npz(path):
+    """{name: array} of a fixture, with the arrays save_npz moved to parts/<file name>."""
+    d = {}
+    for p in (path, _parts_path(path)):
+        if os.path.exists(p):
+            with np.load(p) as z:
+                d.update({k: z[k] for k in z.files})
+    if not d:
+        raise FileNotFoundError(path)
+    return d
 
 
 def save_case(path, sc, steps):
@@ -110,11 +144,11 @@ def save_geom_case(path, sc, outputs):
         d[f"s{i}_V"], d[f"s{i}_F"] = V, F
     for k, v in outputs.items():
         d["out_" + k] = v
-    np.savez_compressed(path, **d)
+    save_npz(path, d)
 
 
 def load_geom_case(name):
-    d = np.load(os.path.join(GOLDEN, name + ".npz"))
+    d = load_npz(os.path.join(GOLDEN, name + ".npz"))
     gs = geom_scenes
     groups = []
     for i, (t, h, k) in enumerate(d["g_meta"]):
@@ -131,7 +165,7 @@ def load_geom_case(name):
                       ref_points=d["ref_points"], surfaces=surfaces, penalty=float(st[0]), iters=int(st[1]),
                       aa_m=int(st[2]), name=name, solver="plain" if len(st) > 4 and st[4] == 1.0 else "alm")
     sc._avg_edge = float(st[3])
-    out = {k[4:]: d[k] for k in d.files if k.startswith("out_")}
+    out = {k[4:]: d[k] for k in d if k.startswith("out_")}
     return sc, out
 
 

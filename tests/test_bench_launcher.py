@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,6 +76,69 @@ def test_bench_gpus2_partitioned_step_on_one_gpu():
     assert line["n_gpus"] == 2
     assert line["config"]["parallelism"] == "mesh-partitioned2 (host)"
     assert line["iters_executed"] == 20 and line["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_their_outputs(pkg, ctx, tmp_path):
+    """A plain run (no --full) times exactly --steps steps, leaves every leg that needs a run of
+    its own out of the line, and --dump-outputs writes what the last timed step returned: the
+    positions, velocities and residual rows of the same scene stepped through the binding."""
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "1", "--config", "c2", "--nx", "24", "--steps", "2",
+                        "--warmup", "1", "--iters", "20", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=110, env=_env(), cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _json_line(r.stdout)
+    assert line["steps"] == 2 and line["iters_executed"] == 40 and line["value"] > 0
+    assert line["ms_per_step"] > 0 and line["unit"] == "ADMM iters/s" and line["dtype"] == "f64"
+    for leg in ("roofline", "time_to_eps", "cpu_baseline"):
+        assert line[leg] is None, leg
+    assert "secondary" not in line
+    assert "reference CPU baseline" not in r.stderr
+    got = {n[:-4]: np.load(out / n) for n in sorted(os.listdir(out))}
+    assert sorted(got) == ["comb", "prim", "v", "x"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    want, solver = pkg.capi.run_scene(ctx, pkg.scenes.cloth(24, 24, iters=20, n_steps=2))
+    solver.close()
+    for name in ("x", "v", "prim", "comb"):
+        assert got[name].shape == want[-1][name].shape, name
+        np.testing.assert_allclose(got[name], want[-1][name], rtol=1e-9, atol=1e-12, err_msg=name)
+
+
+@pytest.mark.gpu
+def test_bench_plain_geometry_run_prints_its_line_and_dumps_the_solution(tmp_path):
+    """The geometry configs' plain run: the line without the --full legs, and the last timed
+    solve's solution and residual curve under --dump-outputs."""
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "1", "--config", "c3", "--nx", "12", "--steps", "2",
+                        "--warmup", "1", "--iters", "20", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=110, env=_env(), cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _json_line(r.stdout)
+    assert line["steps"] == 2 and line["accepted_iters"] == 40 and line["value"] > 0 and line["ms_per_step"] > 0
+    for leg in ("roofline", "run_to_eps", "cpu_baseline"):
+        assert line[leg] is None, leg
+    x, comb = np.load(out / "x.npy"), np.load(out / "comb.npy")
+    assert x.dtype == np.float64 and x.shape == (line["config"]["points"], 3) and np.isfinite(x).all()
+    assert comb.dtype == np.float64 and comb.shape == (20,) and np.isfinite(comb).all()
+
+
+def test_dump_outputs_samples_a_large_array_the_same_way_every_time(tmp_path):
+    """--dump-outputs keeps each array within its byte budget by a fixed, sorted row sample."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    rows = b.DUMP_MAX_BYTES // 24 + 1000
+    big = np.arange(3 * rows, dtype=np.float32).reshape(rows, 3)
+    small = np.arange(5.0)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, a2 = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.nbytes <= b.DUMP_MAX_BYTES and a.shape == (b.DUMP_MAX_BYTES // 24, 3)
+    assert np.array_equal(a, a2) and np.all(np.diff(a[:, 0]) > 0)        # same rows, in order
+    assert np.array_equal(a[:, 1], a[:, 0] + 1)                            # whole rows of the input
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small)
 
 
 def test_time_to_eps_median_counts_unreached_steps():

@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO
-from golden_io import GOLDEN
+from golden_io import GOLDEN, load_npz
 
 FIX = os.path.join(GOLDEN, "quality_reports.npz")
 
@@ -50,7 +50,7 @@ def _check(q, key, names, result_dir, buf):
 
 def test_planarity_report_matches_planarityopt(pkg, tmp_path):
     gr = pkg.geom_report
-    q = np.load(FIX)
+    q = load_npz(FIX)
     g = np.load(os.path.join(GOLDEN, "geom_airport3k_aa10.npz"))
     faces = _faces(q, "pq_airport3k")
     buf = io.StringIO()
@@ -61,8 +61,8 @@ def test_planarity_report_matches_planarityopt(pkg, tmp_path):
 
 def test_wiremesh_report_matches_wiremeshopt(pkg, tmp_path):
     gr = pkg.geom_report
-    q = np.load(FIX)
-    g = np.load(os.path.join(GOLDEN, "geom_costa2k_wire_aa5.npz"))
+    q = load_npz(FIX)
+    g = load_npz(os.path.join(GOLDEN, "geom_costa2k_wire_aa5.npz"))
     # the subdivided quad mesh the solver ran on: 4 angle constraints per face, corner i first
     ang = g["g1_idx"].reshape(-1, 4, 3)
     faces = ang[:, :, 0].tolist()

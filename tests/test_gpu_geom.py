@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from golden_io import GOLDEN, compare_geom, geom_case_names, load_geom_case
+from golden_io import GOLDEN, compare_geom, geom_case_names, load_geom_case, load_npz
 
 pytestmark = pytest.mark.gpu
 
@@ -409,8 +409,8 @@ def test_gpu_quality_reports_match_reference_apps(case, key, pkg, ctx, tmp_path)
     parity bar is 1e-6; corner angles of short edges amplify it)."""
     import io
     gr = pkg.geom_report
-    q = np.load(os.path.join(GOLDEN, "quality_reports.npz"))
-    d = np.load(os.path.join(GOLDEN, case + ".npz"))
+    q = load_npz(os.path.join(GOLDEN, "quality_reports.npz"))
+    d = load_npz(os.path.join(GOLDEN, case + ".npz"))
     sc, ref = load_geom_case(case)
     got, g = pkg.capi.run_geom(ctx, sc)
     closest = lambda P: g.closest_points(0, P)   # noqa: E731

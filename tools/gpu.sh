@@ -53,14 +53,14 @@ for step in "$@"; do
       tail -2 gpurun_out/smoke.log; fatal $rc smoke ;;
     bench)
       cfg=$1; st=${2:-20}; wu=${3:-5}; shift; shift; shift
-      timeout -k 10 ${T_BENCH:-900} python3 -u bench.py --config $cfg --steps $st --warmup $wu "$@" \
+      timeout -k 10 ${T_BENCH:-900} python3 -u bench.py --full --config $cfg --steps $st --warmup $wu "$@" \
         > gpurun_out/bench_$cfg.log 2> gpurun_out/bench_$cfg.err; rc=$?
       cut -c1-300 gpurun_out/bench_$cfg.log; [ $rc -ne 0 ] && tail -20 gpurun_out/bench_$cfg.err; fatal $rc "bench $cfg" ;;
     ab)
       cfg=$1; libs=$2; shift; shift; i=0
       for spec in ${libs//,/ }; do
         i=$((i+1)); log=gpurun_out/ab_${cfg}_$i.log
-        env $(libenv $spec) timeout -k 10 ${T_AB:-300} python -u bench.py --config $cfg --steps ${STEPS:-3} --warmup 1 \
+        env $(libenv $spec) timeout -k 10 ${T_AB:-300} python -u bench.py --full --config $cfg --steps ${STEPS:-3} --warmup 1 \
           --no-cpu-baseline --eps-steps 0 --no-secondary --geom-eps-solves 0 "$@" > $log 2>&1; rc=$?
         [ $rc -ne 0 ] && tail -5 $log; fatal $rc "ab $cfg $spec"
         summ "$i:$spec" $log
@@ -78,7 +78,7 @@ for step in "$@"; do
         d="$R/gpurun_out/pmc_${tag}_${cfg}_${grp//,/_}"
         [ -n "${PMC_KERNEL:-}" ] && d="/tmp/pmc_${tag}_${cfg}_${grp//,/_}"   # raw CSVs stay on the box
         (cd /tmp && TMPDIR=/tmp timeout -k 10 -s KILL 300 rocprofv3 --pmc ${grp//,/ } --output-format csv -d "$d" -o run -- \
-          python3 "$R/bench.py" --config $cfg --steps 1 --warmup 0 --iters ${ITERS:-10} --no-cpu-baseline --eps-steps 0 \
+          python3 "$R/bench.py" --full --config $cfg --steps 1 --warmup 0 --iters ${ITERS:-10} --no-cpu-baseline --eps-steps 0 \
           --no-secondary --geom-eps-solves 0 "$@" > "$d.log" 2>&1); rc=$?
         echo "pmc $grp rc=$rc"; [ $rc -ne 0 ] && grep -v "^ *@" "$d.log" | tail -5; fatal $rc "pmc $grp"
         [ -n "${PMC_KERNEL:-}" ] && python3 tools/pmc_sum.py "$d" "$PMC_KERNEL" "gpurun_out/pmc_${tag}_${cfg}.json"
@@ -86,7 +86,7 @@ for step in "$@"; do
     prof)
       cfg=$1; tag=$2; shift; shift; d="$R/gpurun_out/prof_${tag}_$cfg"
       (cd /tmp && AA_ADMM_NO_GRAPH=1 AA_EAGER_SYNC=10 TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats \
-        --output-format csv -d "$d" -o run -- python3 "$R/bench.py" --config $cfg --steps ${STEPS:-2} --warmup 0 \
+        --output-format csv -d "$d" -o run -- python3 "$R/bench.py" --full --config $cfg --steps ${STEPS:-2} --warmup 0 \
         --no-cpu-baseline --eps-steps 0 --no-secondary --geom-eps-solves 0 "$@" > "$d.log" 2>&1); rc=$?
       echo "prof rc=$rc"; [ $rc -ne 0 ] && grep -v "^ *@" "$d.log" | tail -5; fatal $rc "prof $cfg"
       f=$(find "$d" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -12 "$f" | cut -c1-160
@@ -95,7 +95,7 @@ for step in "$@"; do
     rehearse)   # rehearse CFG P RANK [ENV=V,ENV2=V] [bench args]
       cfg=$1; P=$2; rk=$3; envs=${4:-}; shift; shift; shift; [ $# -gt 0 ] && shift
       log=gpurun_out/rehearse_${cfg}_P${P}_r${rk}_${envs//[,=]/_}.log
-      env ${envs//,/ } timeout -k 10 300 python -u bench.py --config $cfg --rehearse $P --rehearse-rank $rk --steps ${STEPS:-3} \
+      env ${envs//,/ } timeout -k 10 300 python -u bench.py --full --config $cfg --rehearse $P --rehearse-rank $rk --steps ${STEPS:-3} \
         --warmup 1 "$@" > $log 2>&1; rc=$?
       [ $rc -ne 0 ] && tail -5 $log; fatal $rc "rehearse $cfg $P $rk"
       python3 - $log <<'PY'
