@@ -7,7 +7,6 @@
 // comb < eps break) on the device so the whole ADMM loop is enqueued without host syncs.
 #include <algorithm>
 #include <cstdlib>
-#include <type_traits>
 
 #include "common.hpp"
 #include "device_lbfgs.hpp"
@@ -252,15 +251,6 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
     }
 }
 
-// NeoHookean / StVK local step without residual partials (the Z variant's update_z calls), as a
-// persistent work queue: the per-element L-BFGS takes 1..100 iterations, so with one element per
-// lane a wave runs as long as its slowest lane. Here every lane that finishes its element (z and
-// the optional rhs slots written) takes the next one from a queue (one atomic per wave and
-// refill, ballot-aggregated) and lanes advance one outer L-BFGS iteration per trip. Each
-// element's arithmetic is unchanged, so the results are bit-identical to k_local_z.
-// HV: where the L-BFGS history lives -- LQ_HIST_REGS (default): all of it in registers
-// (dev::HyperLbfgs); LQ_HIST_YLDS: the y half in LDS (dev::HyperLbfgsLds, dynamic LDS kLqLdsBytes,
-// AA_LQ_LDS=1; measured slower). Bit-identical.
 // end of a work-queue launch: the last block to finish resets the queue -- claim counter
 // queue[0], finished blocks queue[1] -- for the next launch, which follows a kernel boundary; this
 // replaces a memset node (a fill kernel and its dependency gap) before every launch. A gated
@@ -286,24 +276,22 @@ __device__ __forceinline__ int queue_claim(int* queue, int n) {
     return atomicAdd(queue + off, n);
 }
 
-template <int HV>
-struct LqHist {
-    using type = typename std::conditional<HV == LQ_HIST_YLDS, dev::HyperLbfgsLds, dev::HyperLbfgs>::type;
-};
-
-// CHUNK (AA_LQ_CHUNK=1): the wave claims its elements in chunks of 64 one chunk AHEAD (a
-// wave-uniform range [p0, p1) plus the next chunk's base nx, claimed while the current one is
-// worked on), so a refill's element ids are known without waiting for the queue atomic: the refill
-// chain is node ids -> positions instead of atomic -> node ids -> positions. The last chunks (the
-// queue within `margin` elements of its end) are claimed at the refill, as CHUNK = 0 does, so no
-// wave sits on unstarted elements while others run dry. Same elements, same arithmetic per
-// element: bit-identical outputs.
-template <int NV, int HV, int CHUNK = 0>
+// NeoHookean / StVK local step without residual partials (the Z variant's update_z calls), as a
+// persistent work queue: the per-element L-BFGS takes 1..100 iterations, so with one element per
+// lane a wave runs as long as its slowest lane. Here every lane that finishes its element takes
+// the next one from a queue (one atomic per wave and refill, ballot-aggregated) and lanes advance
+// one outer L-BFGS iteration per trip. Each element's arithmetic is unchanged, so the results are
+// bit-identical to k_local_z. This is the plain refill: claim, write the finished elements' z and
+// optional rhs slots, gather the new elements -- each a dependent round trip. Groups with pinned
+// nodes use it (their Cp needs the finished element's positions), as do AA_LQ_FUSED=0 and
+// AA_LQ_FUSED_CONC=0; every other queue launch is k_local_z_hqf below, whose bit-identity
+// baseline this kernel is.
+template <int NV>
 __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double* __restrict__ xfull,
                                                        const double* __restrict__ u, double* __restrict__ z,
                                                        double* __restrict__ y, int nf, int mode, Ctrl* ctrl,
                                                        int* __restrict__ queue, int refill,
-                                                       unsigned long long* __restrict__ stats, int margin = 0) {
+                                                       unsigned long long* __restrict__ stats) {
     if (mode != LZ_INIT && gated(ctrl, mode == LZ_REDO)) return;
     unsigned trips = 0, refills = 0;
     __shared__ unsigned hist[101];   // diagnostics only: per-block histogram, flushed at the end
@@ -313,11 +301,7 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
     }
     constexpr int D = 3 * (NV - 1);
     const int lane = threadIdx.x & 63;
-    typename LqHist<HV>::type L;
-    if constexpr (HV == LQ_HIST_YLDS) {
-        extern __shared__ double lq_hist[];
-        L.bind(lq_hist + threadIdx.x, kBlock);
-    }
+    dev::HyperLbfgs L;
     double v[D], x[D];
     double vol = 0;
     int e = -1, fail = 0;
@@ -326,13 +310,6 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
     // wave pays the gathers' latency once per refill instead of on every trip in which some
     // lane finishes
     bool active = false, pending = false, exhausted = false;
-    // CHUNK: the wave's claimed, unstarted range [p0, p1); nxv = lane 0's last queue atomic
-    // result; ahead = a 64-chunk claim is in flight; qpos = the last queue position seen
-    // (nxs: nxv read back at the end of the refill that issued it -- a wait there costs nothing, the
-    // refill's later gathers have returned; a read at the next refill would wait for that refill's
-    // finalize stores too, the vector memory counter being in order)
-    int p0 = 0, p1 = 0, nxv = 0, nxs = 0, qpos = 0;
-    bool ahead = false, fresh = false;
     auto finalize = [&]() {
 #pragma unroll
         for (int i = 0; i < D; ++i) z[g.zoff + (size_t)i * g.count + e] = x[i];
@@ -354,46 +331,13 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
             const int leader = __ffsll((long long)mask) - 1;
             const int k = __popcll(mask), rank = __popcll(mask & ((1ull << lane) - 1ull));
             int b = 0, my = 0;
-            if constexpr (CHUNK == 0) {
-                if (lane == leader) b = queue_claim(queue, k);
-            } else if (!ahead && qpos + 64 <= g.count - margin) {   // the next chunk, ahead of need
-                // (issued before the finalize, like CHUNK = 0's claim, so its round trip hides
-                // under the finalize's gathers when this refill already needs it)
-                if (lane == 0) nxv = atomicAdd(queue, 64);
-                ahead = true;
-                fresh = true;
-            }
+            if (lane == leader) b = queue_claim(queue, k);
             if (pending) {
                 finalize();
                 pending = false;
             }
-            if constexpr (CHUNK == 0) {
-                b = __shfl(b, leader, 64);
-                my = b + rank;
-            } else {
-                // exec is full here (the refill test is wave-uniform, all lanes stay in the loop
-                // until the wave breaks), so lane 0 issues the claims and readfirstlane reads it
-                const int avail = p1 - p0;
-                if (avail >= k) {
-                    my = p0 + rank;
-                    p0 += k;
-                } else {
-                    int hi;
-                    if (ahead) {   // the chunk claimed ahead: 64 more
-                        hi = fresh ? __builtin_amdgcn_readfirstlane(nxv) : nxs;
-                        p1 = hi + 64;
-                    } else {       // first refill, or the tail: claim exactly what is missing, now
-                        if (lane == 0) nxv = atomicAdd(queue, k - avail);
-                        hi = __builtin_amdgcn_readfirstlane(nxv);
-                        p1 = hi + (k - avail);
-                    }
-                    my = rank < avail ? p0 + rank : hi + (rank - avail);
-                    p0 = hi + (k - avail);
-                    qpos = hi;
-                    ahead = false;
-                    fresh = false;
-                }
-            }
+            b = __shfl(b, leader, 64);
+            my = b + rank;
             if (need) {
                 if (my >= g.count) {
                     exhausted = true;
@@ -416,12 +360,6 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
                     } else {
                         active = true;
                     }
-                }
-            }
-            if constexpr (CHUNK != 0) {
-                if (fresh) {   // claimed at this refill, not used yet: read it back now
-                    nxs = __builtin_amdgcn_readfirstlane(nxv);
-                    fresh = false;
                 }
             }
         }
@@ -457,8 +395,9 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
 // element's positions, coefficients, u, w and vol. A start point that already passes the gradient
 // test leaves its element pending (written at the next refill) instead of writing it at once.
 // Same arithmetic in the same order: bit-identical. 452 registers (one wave per SIMD, as the
-// plain kernel's 402) -- too many to leave the Anderson kernels room beside it, so the concurrent
-// combined-residual pass keeps the plain refill (ElasticSolver::initialize). C4 (same box, two A/B
+// plain kernel's 402), which leave the Anderson kernels no room beside it on a SIMD. The concurrent
+// combined-residual pass writes no slots and runs SLOTS = false: without the slot loads it holds
+// 412 registers, which do leave that room (ElasticSolver::initialize). C4 (same box, two A/B
 // pairs): local_z 433 / 435 -> 422 / 418 us.
 template <int NV, bool SLOTS = true>
 __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double* __restrict__ xfull,
@@ -720,179 +659,6 @@ __global__ __launch_bounds__(kBlock, 2) void k_local_z_hq2(GroupDev g, const dou
             active = false;
             pending = true;
             if (stats && h == 0) atomicAdd(&hist[min(L.k_it, 100)], 1u);
-        }
-    }
-    if (stats) {
-        if (lane == 0) {
-            atomicAdd(stats + 101, (unsigned long long)trips);
-            atomicAdd(stats + 102, (unsigned long long)refills);
-            atomicAdd(stats + 103, 1ull);
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < 101; i += blockDim.x)
-            if (hist[i]) atomicAdd(stats + i, (unsigned long long)hist[i]);
-    }
-    if (fail && ctrl) ctrl->fail = 1;
-}
-
-// k_local_z_hq with a one-element lookahead per lane (AA_LQ_AHEAD=1; measured 6 % slower than
-// k_local_z_hq on C4). A refill of the plain queue is a chain of three dependent round trips -- the
-// returning queue atomic, the element's node ids, then the node positions -- paid while the wave's
-// other lanes wait (28 % of the kernel's cycles at one wave per SIMD). Here each
-// lane holds its NEXT element: the claim atomic is issued at a refill and read on the next trip,
-// the node ids are loaded right then, so the following refill only waits for the positions /
-// coefficient / u loads, all independent (one round trip). The finalize keeps the element's node
-// ids and loads positions only for pinned nodes (the only ones Cp needs). Close to the end of the
-// queue (fewer than `margin` elements left) lookahead stops, so claimed-ahead elements cannot
-// pile up on a few waves. Same arithmetic per element: bit-identical to k_local_z_hq.
-template <int NV, int HV>
-__global__ __launch_bounds__(kBlock) void k_local_z_hqa(GroupDev g, const double* __restrict__ xfull,
-                                                        const double* __restrict__ u, double* __restrict__ z,
-                                                        double* __restrict__ y, int nf, int mode, Ctrl* ctrl,
-                                                        int* __restrict__ queue, int refill, int margin,
-                                                        unsigned long long* __restrict__ stats) {
-    if (mode != LZ_INIT && gated(ctrl, mode == LZ_REDO)) return;
-    unsigned trips = 0, refills = 0;
-    __shared__ unsigned hist[101];
-    if (stats) {
-        for (int i = threadIdx.x; i < 101; i += blockDim.x) hist[i] = 0;
-        __syncthreads();
-    }
-    constexpr int D = 3 * (NV - 1), NC = NV - 1;
-    const int lane = threadIdx.x & 63;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    typename LqHist<HV>::type L;
-    if constexpr (HV == LQ_HIST_YLDS) {
-        extern __shared__ double lq_hist[];
-        L.bind(lq_hist + threadIdx.x, kBlock);
-    }
-    double v[D], x[D];
-    double vol = 0;
-    int e = -1, fail = 0;
-    int nid[NV];                 // node ids of the lane's element
-    int ex = -1, xid[NV];        // lookahead element and its node ids
-    int stage = 0, ab = 0, aleader = 0;   // stage 1: a lookahead claim (atomic) is in flight
-    unsigned long long amask = 0;
-    bool active = false, pending = false, exhausted = false, dry = false;
-#pragma unroll
-    for (int a = 0; a < NV; ++a) { nid[a] = 0; xid[a] = 0; }
-    auto finalize = [&]() {
-#pragma unroll
-        for (int i = 0; i < D; ++i) z[g.zoff + (size_t)i * g.count + e] = x[i];
-        if (y) {
-            double Cp[D], uu[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) Cp[i] = 0;
-#pragma unroll
-            for (int a = 0; a < NV; ++a) {   // gather_F's Cp: pinned nodes only, same order
-                const int vv = nid[a];
-                if (vv >= nf) {
-                    const double x0 = xfull[3 * (size_t)vv], x1 = xfull[3 * (size_t)vv + 1], x2 = xfull[3 * (size_t)vv + 2];
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        const double gc = g.G[(size_t)(c * NV + a) * g.count + e];
-                        Cp[3 * c + 0] += gc * x0; Cp[3 * c + 1] += gc * x1; Cp[3 * c + 2] += gc * x2;
-                    }
-                }
-            }
-            load_u<D>(g, e, u, uu);
-            write_slots<NV>(g, e, nf, g.w[e], x, Cp, uu, y);
-        }
-    };
-    auto begin = [&](int ee, const int* ids) {
-        e = ee;
-        double F[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) F[i] = 0;
-#pragma unroll
-        for (int a = 0; a < NV; ++a) {   // gather_F's F, same order
-            nid[a] = ids[a];
-            const double x0 = xfull[3 * (size_t)ids[a]], x1 = xfull[3 * (size_t)ids[a] + 1], x2 = xfull[3 * (size_t)ids[a] + 2];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const double gc = g.G[(size_t)(c * NV + a) * g.count + e];
-                F[3 * c + 0] += gc * x0; F[3 * c + 1] += gc * x1; F[3 * c + 2] += gc * x2;
-            }
-        }
-        const double w = g.w[e];
-        double uu[D];
-        load_u<D>(g, e, u, uu);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            v[i] = F[i] + uu[i] / w;
-            x[i] = v[i];
-        }
-        vol = g.vol[e];
-        if (L.start(g.mat, g.mu, g.lambda, g.k, vol, v, x)) {
-            finalize();
-            if (stats) atomicAdd(&hist[0], 1u);
-        } else {
-            active = true;
-        }
-    };
-    for (;;) {
-        const bool need = !active && !exhausted;
-        const unsigned long long mask = __ballot(need);
-        if (!__any(active || need)) break;
-        ++trips;
-        if (stage == 1) {   // the lookahead claim issued at the last refill has returned
-            const int b = __shfl(ab, aleader, 64);
-            if ((amask >> lane) & 1ull) {
-                const int my = b + __popcll(amask & below);
-                if (my < g.count) {
-                    ex = my;
-#pragma unroll
-                    for (int a = 0; a < NV; ++a) xid[a] = g.idx[(size_t)a * g.count + ex];
-                }
-            }
-            if (b + __popcll(amask) >= g.count - margin) dry = true;
-            stage = 0;
-        }
-        if (mask && (__popcll(mask) >= refill || !__any(active))) {
-            ++refills;
-            const bool direct = need && ex < 0;   // no lookahead: claim now (queue start, its tail)
-            const unsigned long long dmask = __ballot(direct);
-            int b = 0, leader = 0;
-            if (dmask) {
-                leader = __ffsll((long long)dmask) - 1;
-                if (lane == leader) b = atomicAdd(queue, __popcll(dmask));
-            }
-            if (pending) {
-                finalize();
-                pending = false;
-            }
-            int ee = -1, ids[NV];
-#pragma unroll
-            for (int a = 0; a < NV; ++a) ids[a] = xid[a];
-            if (need && ex >= 0) { ee = ex; ex = -1; }
-            if (dmask) {
-                b = __shfl(b, leader, 64);
-                if (direct) {
-                    const int my = b + __popcll(dmask & below);
-                    if (my >= g.count) {
-                        exhausted = true;
-                    } else {
-                        ee = my;
-#pragma unroll
-                        for (int a = 0; a < NV; ++a) ids[a] = g.idx[(size_t)a * g.count + ee];
-                    }
-                }
-            }
-            if (ee >= 0) begin(ee, ids);
-            if (!dry) {   // the next lookahead claim, for every lane without one
-                const unsigned long long lm = __ballot(ex < 0 && !exhausted);
-                if (lm) {
-                    amask = lm;
-                    aleader = __ffsll((long long)lm) - 1;
-                    if (lane == aleader) ab = atomicAdd(queue, __popcll(lm));
-                    stage = 1;
-                }
-            }
-        }
-        if (active && L.iterate(g.mat, g.mu, g.lambda, g.k, vol, v, x, &fail)) {
-            active = false;
-            pending = true;
-            if (stats) atomicAdd(&hist[min(L.k_it, 100)], 1u);
         }
     }
     if (stats) {
@@ -1894,35 +1660,17 @@ LocalQueue make_local_queue(int device, int* counter) {
     int cus = 0, per = 0;
     AA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     const char* r = std::getenv("AA_LQ_REFILL");
-    const char* ah = std::getenv("AA_LQ_AHEAD");
-    const char* lh = std::getenv("AA_LQ_LDS");
-    q.ahead = ah && ah[0] == '1';   // opt-in: measured slower on C4
-    q.hist = (lh && lh[0] == '1') ? LQ_HIST_YLDS : LQ_HIST_REGS;   // opt-in: no faster on C4
     const char* sp = std::getenv("AA_LQ_SPLIT");
-    q.split = sp ? sp[0] == '1' : false;
-    if (q.split) q.ahead = false, q.hist = LQ_HIST_REGS;
-    const char* ck = std::getenv("AA_LQ_CHUNK");
-    q.chunk = ck && ck[0] == '1' && !q.split && !q.ahead && q.hist == LQ_HIST_REGS;
+    q.split = sp && sp[0] == '1';   // opt-in: measured slower on C4
     const char* fu = std::getenv("AA_LQ_FUSED");
-    // default on (AA_LQ_FUSED=0: the plain refill); the caller turns it off for the concurrent pass
-    q.fused = (fu ? fu[0] == '1' : true) && !q.split && !q.ahead && !q.chunk && q.hist == LQ_HIST_REGS;
+    // default on (AA_LQ_FUSED=0: the plain refill); the caller may turn it off for the concurrent pass
+    q.fused = (fu ? fu[0] == '1' : true) && !q.split;
     const void* kq = q.fused ? (const void*)k_local_z_hqf<4>
-                   : q.chunk ? (const void*)k_local_z_hq<4, LQ_HIST_REGS, 1>
-                   : q.split ? (const void*)k_local_z_hq2<4>
-                   : q.ahead ? (q.hist == LQ_HIST_YLDS ? (const void*)k_local_z_hqa<4, LQ_HIST_YLDS>
-                                                       : (const void*)k_local_z_hqa<4, LQ_HIST_REGS>)
-                             : (q.hist == LQ_HIST_YLDS ? (const void*)k_local_z_hq<4, LQ_HIST_YLDS>
-                                                       : (const void*)k_local_z_hq<4, LQ_HIST_REGS>);
-    const size_t lds = q.hist == LQ_HIST_YLDS ? kLqLdsBytes : 0;
-    q.lds_bytes = lds;
-    if (lds) AA_HIP(hipFuncSetAttribute(kq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    AA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kq, kBlock, lds));
+                   : q.split ? (const void*)k_local_z_hq2<4> : (const void*)k_local_z_hq<4>;
+    AA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kq, kBlock, 0));
     q.resident = std::max(1, cus * std::max(1, per));
     q.refill = r ? std::atoi(r) : 60;
     if (q.split) q.refill = std::max(1, (q.refill + 1) / 2);   // in pairs (elements) per wave
-    // lookahead stops once fewer elements than this are left (AA_LQ_MARGIN: in resident lanes)
-    const char* mg = std::getenv("AA_LQ_MARGIN");
-    q.margin = (int)(std::max(0.0, mg ? std::atof(mg) : 1.0) * q.resident * kBlock);
     return q;
 }
 
@@ -1931,36 +1679,22 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
     if (g.kind == 0 && g.mat != 0 && !red && queue && queue->counter) {   // hyperelastic, no partials: work queue
-        // k_local_z_hq / k_local_z_hqf reset the queue themselves (queue_reset_last)
-        if (queue->split || queue->ahead) AA_HIP(hipMemsetAsync(queue->counter, 0, sizeof(int), s));
+        // k_local_z_hq / k_local_z_hqf reset the queue themselves (queue_reset_last); k_local_z_hq2 does not
+        if (queue->split) AA_HIP(hipMemsetAsync(queue->counter, 0, sizeof(int), s));
         const int resident = std::max(1, queue->resident), refill = queue->refill;
         const dim3 grid(std::min(nb, resident));
-        const size_t lds = queue->lds_bytes;
         if (queue->split) {   // two lanes per element: half the elements per block
             const dim3 grid2(std::min(blocks_for(2LL * g.count), resident));
             hipLaunchKernelGGL((k_local_z_hq2<4>), grid2, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode, ctrl,
                                queue->counter, refill, queue->stats);
-        } else if (queue->ahead && queue->hist == LQ_HIST_YLDS)
-            hipLaunchKernelGGL((k_local_z_hqa<4, LQ_HIST_YLDS>), grid, dim3(kBlock), lds, s, g, xfull, u, z, y, nf, mode,
-                               ctrl, queue->counter, refill, queue->margin, queue->stats);
-        else if (queue->ahead)
-            hipLaunchKernelGGL((k_local_z_hqa<4, LQ_HIST_REGS>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode,
-                               ctrl, queue->counter, refill, queue->margin, queue->stats);
-        else if (queue->fused && !g.pinned)   // pinned groups keep the plain refill (their Cp needs positions)
-        {
-            if (y) hipLaunchKernelGGL((k_local_z_hqf<4, true>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode,
-                                      ctrl, queue->counter, refill, queue->stats);
-            else hipLaunchKernelGGL((k_local_z_hqf<4, false>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode,
-                                    ctrl, queue->counter, refill, queue->stats);
-        }
-        else if (queue->chunk)
-            hipLaunchKernelGGL((k_local_z_hq<4, LQ_HIST_REGS, 1>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf,
-                               mode, ctrl, queue->counter, refill, queue->stats, queue->margin);
-        else if (queue->hist == LQ_HIST_YLDS)
-            hipLaunchKernelGGL((k_local_z_hq<4, LQ_HIST_YLDS>), grid, dim3(kBlock), lds, s, g, xfull, u, z, y, nf, mode,
+        } else if (!queue->fused || g.pinned)   // pinned groups keep the plain refill (their Cp needs positions)
+            hipLaunchKernelGGL((k_local_z_hq<4>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode, ctrl,
+                               queue->counter, refill, queue->stats);
+        else if (y)
+            hipLaunchKernelGGL((k_local_z_hqf<4, true>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode,
                                ctrl, queue->counter, refill, queue->stats);
         else
-            hipLaunchKernelGGL((k_local_z_hq<4, LQ_HIST_REGS>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode,
+            hipLaunchKernelGGL((k_local_z_hqf<4, false>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode,
                                ctrl, queue->counter, refill, queue->stats);
         AA_CHECK_LAUNCH();
         return;

@@ -75,20 +75,16 @@ enum LocalMode { LZ_NORMAL = 0, LZ_REDO = 1, LZ_INIT = 2 };
 // device and the refill threshold (computed once per solver, make_local_queue)
 struct LocalQueue {
     int* counter = nullptr;
-    int resident = 0, refill = 60, margin = 0;
-    bool ahead = false;  // AA_LQ_AHEAD=1: k_local_z_hqa (one-element lookahead per lane)
+    int resident = 0, refill = 60;
+    // k_local_z_hqf (the refill's loads regrouped; groups without pins) instead of the plain
+    // k_local_z_hq: the default, AA_LQ_FUSED=0 turns it off
+    bool fused = false;
     bool split = false;  // AA_LQ_SPLIT=1: k_local_z_hq2 (each element's L-BFGS over a lane pair)
-    bool fused = false;  // AA_LQ_FUSED=1: k_local_z_hqf (the refill's loads regrouped; groups without pins)
-    bool chunk = false;  // AA_LQ_CHUNK=1: k_local_z_hq<4, REGS, 1> (64-element chunks claimed one ahead)
-    int hist = 0;        // LqHistory: where the L-BFGS history lives (AA_LQ_LDS=1: y half in LDS)
-    size_t lds_bytes = 0;
     // optional diagnostics (AA_LQ_STATS=1): [0..100] elements by L-BFGS iterations (0 = the start
     // point passed the gradient test), [101] trips, [102] refills, [103] waves; summed over launches
     unsigned long long* stats = nullptr;
 };
 constexpr int kLqStats = 104;
-constexpr size_t kLqLdsBytes = sizeof(double) * 6 * 10 * kBlock;   // HyperLbfgsLds ring, one block
-enum LqHistory { LQ_HIST_REGS = 0, LQ_HIST_YLDS = 1 };
 LocalQueue make_local_queue(int device, int* counter);
 // z = prox(P x + u/w); prim partials; optional y = w(w z + c - u). gate: !done (and reject for REDO)
 // queue given: hyperelastic groups without partials run as a persistent work queue

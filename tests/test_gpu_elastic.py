@@ -273,29 +273,16 @@ def test_gpu_fused_subtrees_lds_vectors_bit_identical(pkg, ctx, monkeypatch, cap
             assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), (k, len(a["comb"]), len(b["comb"]))
 
 
-@pytest.mark.parametrize("ahead", ["0", "1"])
-def test_gpu_local_queue_lds_history_bit_identical(pkg, ctx, monkeypatch, ahead):
-    """The NeoHookean local step with the L-BFGS history's y half in LDS (dev::HyperLbfgsLds, a
-    ring per lane) against the all-register history (AA_LQ_LDS=0), with and without the lookahead
-    queue: the same operations in the same order (TetEnergyTerm.cpp:151-162 via mcloptlib
-    LBFGS.hpp:205-305), so bit-identical trajectories."""
-    sc = scenes.tet_drop(12, 4, 6, iters=30, n_steps=2)
-    monkeypatch.setenv("AA_LQ_AHEAD", ahead)
-    monkeypatch.setenv("AA_LQ_LDS", "0")
-    reg, _ = pkg.capi.run_scene(ctx, sc)
-    monkeypatch.setenv("AA_LQ_LDS", "1")
-    lds, _ = pkg.capi.run_scene(ctx, sc)
-    for a, b in zip(reg, lds):
-        for k in ("prim", "comb", "reject", "x", "v"):
-            assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k
-
-
 @pytest.mark.parametrize("scene", ["drop_x", "drop_h", "cantilever_pinned"])
 def test_gpu_local_queue_fused_refill_bit_identical(pkg, ctx, monkeypatch, scene):
     """The default work queue's refill with its loads regrouped (k_local_z_hqf) against the plain
     refill (AA_LQ_FUSED=0): each element's L-BFGS (TetEnergyTerm.cpp:151-162) and its outputs --
     z and the rhs slots w (w z - u) (Solver.cpp:105/175) -- are the same operations in the same
-    order, so bit-identical trajectories; a pinned group (the cantilever) keeps the plain refill."""
+    order, so bit-identical trajectories; a pinned group (the cantilever) keeps the plain refill.
+    drop_x is the z-AA solver (scenes.VARIANT_X = AA_VARIANT_Z), pipelined with the concurrent
+    combined-residual pass on by default, so that case is the headline config's default path:
+    k_local_z_hqf<4, true> at LZ_NORMAL plus k_local_z_hqf<4, false> beside it, against
+    k_local_z_hq on both."""
     if scene == "cantilever_pinned":
         sc = scenes.cantilever(12, 3, 3, iters=30, n_steps=2)
     else:
@@ -306,24 +293,6 @@ def test_gpu_local_queue_fused_refill_bit_identical(pkg, ctx, monkeypatch, scene
     monkeypatch.setenv("AA_LQ_FUSED", "1")
     fused, _ = pkg.capi.run_scene(ctx, sc)
     for a, b in zip(base, fused):
-        for k in ("prim", "comb", "reject", "x", "v"):
-            assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k
-
-
-@pytest.mark.parametrize("margin", ["0", "0.05"])
-def test_gpu_local_queue_chunked_claim_bit_identical(pkg, ctx, monkeypatch, margin):
-    """The work queue with 64-element chunks claimed one ahead (AA_LQ_CHUNK=1, opt-in) against the
-    per-refill claim: each element is still solved by one lane with the same operations
-    (TetEnergyTerm.cpp:151-162), only which lane and when differ, so bit-identical trajectories.
-    AA_LQ_MARGIN=0 runs the claim-ahead path to the queue's end; 0.05 of the resident lanes
-    switches to exact claims for the tail."""
-    sc = scenes.tet_drop(16, 6, 8, iters=30, n_steps=2)
-    monkeypatch.setenv("AA_LQ_MARGIN", margin)
-    monkeypatch.setenv("AA_LQ_CHUNK", "0")
-    base, _ = pkg.capi.run_scene(ctx, sc)
-    monkeypatch.setenv("AA_LQ_CHUNK", "1")
-    chunk, _ = pkg.capi.run_scene(ctx, sc)
-    for a, b in zip(base, chunk):
         for k in ("prim", "comb", "reject", "x", "v"):
             assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k
 
