@@ -23,7 +23,7 @@ EXPORTS = [
     "aa_last_error", "aa_version", "aa_ctx_create", "aa_ctx_destroy", "aa_ctx_synchronize", "aa_ctx_bench_read",
     "aa_ctx_warm_dense", "aa_lame_from_young",
     "aa_settings_default", "aa_elastic_create", "aa_elastic_destroy", "aa_elastic_add_nodes", "aa_elastic_add_tets",
-    "aa_elastic_add_tris", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
+    "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
     "aa_elastic_add_obstacle", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
     "aa_elastic_num_nodes", "aa_elastic_get_x", "aa_elastic_get_v", "aa_elastic_set_v", "aa_elastic_get_history",
     "aa_elastic_get_times", "aa_elastic_set_iterations", "aa_elastic_set_x",
@@ -303,6 +303,33 @@ class Solver:
         _chk(lib().aa_elastic_add_tris(self.h, _dp(v), _ip(t), C.c_int(len(t) // 3), C.byref(lame),
                                        C.c_int(vertex_offset)))
 
+    @staticmethod
+    def _lame_array(n, mu, lam, limit_min=None, limit_max=None):
+        """[n] aa_lame records from per-element arrays (scalars broadcast; limits default to Lame's)."""
+        a = np.empty((n, 4), np.float64)
+        a[:, 0] = mu
+        a[:, 1] = lam
+        a[:, 2] = -100.0 if limit_min is None else limit_min
+        a[:, 3] = 100.0 if limit_max is None else limit_max
+        return a
+
+    def add_tets_var(self, verts, tets, material, mu, lam, vertex_offset=0):
+        """One group of tets with per-element Lame parameters (aa_elastic_add_tets_var): mu, lam are
+        arrays of the group's length -- the reference's loop of one-element create_tets_from_mesh calls."""
+        v = np.ascontiguousarray(verts, np.float64).reshape(-1)
+        t = np.ascontiguousarray(tets, np.int32).reshape(-1)
+        la = self._lame_array(len(t) // 4, mu, lam)
+        _chk(lib().aa_elastic_add_tets_var(self.h, _dp(v), _ip(t), C.c_int(len(t) // 4), C.c_int(material),
+                                           la.ctypes.data_as(C.POINTER(Lame)), C.c_int(vertex_offset)))
+
+    def add_tris_var(self, verts, tris, mu, lam, limit_min=None, limit_max=None, vertex_offset=0):
+        """One group of triangles with per-element Lame parameters and strain limits (aa_elastic_add_tris_var)."""
+        v = np.ascontiguousarray(verts, np.float64).reshape(-1)
+        t = np.ascontiguousarray(tris, np.int32).reshape(-1)
+        la = self._lame_array(len(t) // 3, mu, lam, limit_min, limit_max)
+        _chk(lib().aa_elastic_add_tris_var(self.h, _dp(v), _ip(t), C.c_int(len(t) // 3),
+                                           la.ctypes.data_as(C.POINTER(Lame)), C.c_int(vertex_offset)))
+
     def set_pins(self, inds, points=None):
         i = np.ascontiguousarray(inds, np.int32).reshape(-1)
         if points is None:
@@ -439,6 +466,15 @@ def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
         s.set_comm(comm)
     s.add_nodes(scene.x, np.repeat(np.asarray(scene.masses, np.float64), 3))
     for g in scene.groups:
+        if g.per_element:   # arrays of the group's length: one group with per-element materials
+            E, nu, lmin, lmax = g.material_arrays()
+            mu = E / (2.0 * (1.0 + nu))    # Lame.from_young's expressions, per element
+            lam = E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+            if g.kind == 0:
+                s.add_tets_var(scene.rest_x, g.idx, g.material, mu, lam)
+            else:
+                s.add_tris_var(scene.rest_x, g.idx, mu, lam, lmin, lmax)
+            continue
         lame = Lame.from_young(g.E, g.nu, g.limit_min, g.limit_max)
         if g.kind == 0:
             s.add_tets(scene.rest_x, g.idx, g.material, lame)

@@ -158,6 +158,24 @@ int aa_elastic_add_tris(aa_elastic h, const double* verts3, const int* tris3, in
     });
 }
 
+int aa_elastic_add_tets_var(aa_elastic h, const double* verts3, const int* tets4, int n, int material,
+                            const aa_lame* lame_per_tet, int vertex_offset) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        NEED(lame_per_tet || n <= 0, "add_tets_var: null material array");
+        h->s->add_elements(0, material, verts3, tets4, n, aa_lame{}, vertex_offset, n > 0 ? lame_per_tet : nullptr);
+    });
+}
+
+int aa_elastic_add_tris_var(aa_elastic h, const double* verts3, const int* tris3, int n, const aa_lame* lame_per_tri,
+                            int vertex_offset) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        NEED(lame_per_tri || n <= 0, "add_tris_var: null material array");
+        h->s->add_elements(1, AA_LINEAR, verts3, tris3, n, aa_lame{}, vertex_offset, n > 0 ? lame_per_tri : nullptr);
+    });
+}
+
 int aa_elastic_set_pins(aa_elastic h, const int* inds, const double* pts3, int n) {
     return guarded([&] { NEED(h, "null handle"); h->s->set_pins(inds, pts3, n); });
 }

@@ -50,25 +50,45 @@ int ElasticSolver::add_nodes(const double* x3, const double* m3, int n) {
 
 // TetEnergyTerm ctor + get_reduction (TetEnergyTerm.cpp:32-72), TriEnergyTerm ctor +
 // get_reduction (TriEnergyTerm.cpp:30-72), EnergyTerm::get_reduction weight check (EnergyTerm.hpp:135-153)
+// per_element: the reference's one EnergyTerm per element, each with its own Lame (TetEnergyTerm.hpp:36-51,
+// TriEnergyTerm.hpp:33-47) -- n create_*_from_mesh calls of one element each, in element order, as one
+// group. The scalar calls' checks apply per element; the message names the first offending element.
 void ElasticSolver::add_elements(int kind, int material, const double* verts3, const int* idx, int count,
-                                 const aa_lame& lame, int vertex_offset) {
+                                 const aa_lame& lame, int vertex_offset, const aa_lame* per) {
     if (count < 0 || (count > 0 && (!verts3 || !idx))) throw Error(ERR_ARG, "add_elements: bad input");
     if (initialized_) throw Error(ERR_STATE, "adding energy terms after initialize is not supported");
-    if (kind == 1) {
-        if (lame.limit_min > 1.0) throw Error(ERR_ARG, "**TriEnergyTerm Error: Strain limit min should be -inf to 1");
-        if (lame.limit_max < 1.0) throw Error(ERR_ARG, "**TriEnergyTerm Error: Strain limit max should be 1 to inf");
-        material = AA_LINEAR;
-    } else if (material < 0 || material > 2) {
-        throw Error(ERR_ARG, "add_tets: unknown material");
-    }
+    auto at = [&](const char* msg, int t) {
+        return per ? std::string(msg) + " (element " + std::to_string(t) + ")" : std::string(msg);
+    };
+    // one element's Lame: the TriEnergyTerm ctor's range checks (TriEnergyTerm.cpp:30-40)
+    auto check_lame = [&](const aa_lame& l, int t) {
+        if (per && (!std::isfinite(l.mu) || !std::isfinite(l.lambda)))
+            throw Error(ERR_ARG, at("add_elements: mu and lambda must be finite", t));
+        if (kind != 1) return;
+        if (l.limit_min > 1.0) throw Error(ERR_ARG, at("**TriEnergyTerm Error: Strain limit min should be -inf to 1", t));
+        if (l.limit_max < 1.0) throw Error(ERR_ARG, at("**TriEnergyTerm Error: Strain limit max should be 1 to inf", t));
+    };
+    if (kind == 1) material = AA_LINEAR;
+    else if (material < 0 || material > 2) throw Error(ERR_ARG, "add_tets: unknown material");
+    if (!per) check_lame(lame, 0);
     HostGroup g;
-    g.kind = kind; g.material = material; g.lame = lame;
+    g.kind = kind; g.material = material; g.lame = per ? aa_lame{} : lame;
     g.nv = kind == 0 ? 4 : 3; g.ncol = g.nv - 1;
-    const double k = lame.lambda + (2.0 / 3.0) * lame.mu;
+    double k = lame.lambda + (2.0 / 3.0) * lame.mu;
+    if (per) {
+        g.mu_e.resize(count); g.lambda_e.resize(count); g.k_e.resize(count);
+        if (kind == 1) { g.lmin_e.resize(count); g.lmax_e.resize(count); }
+    }
     g.idx.resize((size_t)count * g.nv);
     g.G.resize((size_t)count * g.ncol * g.nv);
     g.vol.resize(count); g.w.resize(count);
     for (int t = 0; t < count; ++t) {
+        if (per) {   // element t's own term: its checks come before the next element's, as in a caller's loop
+            check_lame(per[t], t);
+            g.mu_e[t] = per[t].mu; g.lambda_e[t] = per[t].lambda;
+            g.k_e[t] = k = per[t].lambda + (2.0 / 3.0) * per[t].mu;
+            if (kind == 1) { g.lmin_e[t] = per[t].limit_min; g.lmax_e[t] = per[t].limit_max; }
+        }
         const double* P[4];
         for (int a = 0; a < g.nv; ++a) {
             const int li = idx[(size_t)t * g.nv + a];
@@ -89,7 +109,7 @@ void ElasticSolver::add_elements(int kind, int material, const double* verts3, c
             double Bi[9];
             for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Bi[r * 3 + c] = cof[c * 3 + r] / det;
             vol = det / 6.0;
-            if (vol < 0) throw Error(ERR_NUMERIC, "**TetEnergyTerm Error: Inverted initial tet");
+            if (vol < 0) throw Error(ERR_NUMERIC, at("**TetEnergyTerm Error: Inverted initial tet", t));
             for (int r = 0; r < 3; ++r) {
                 G[r * 4 + 0] = -Bi[0 * 3 + r] - Bi[1 * 3 + r] - Bi[2 * 3 + r];
                 for (int a = 1; a < 4; ++a) G[r * 4 + a] = Bi[(a - 1) * 3 + r];
@@ -109,7 +129,7 @@ void ElasticSolver::add_elements(int kind, int material, const double* verts3, c
             const double invdet = 1.0 / det;
             const double R[2][2] = {{b11 * invdet, -b01 * invdet}, {-b10 * invdet, b00 * invdet}};
             vol = 0.5 * det;
-            if (vol < 0) throw Error(ERR_NUMERIC, "**TriEnergyTerm Error: Inverted initial pose");
+            if (vol < 0) throw Error(ERR_NUMERIC, at("**TriEnergyTerm Error: Inverted initial pose", t));
             for (int c = 0; c < 2; ++c) {
                 G[c * 3 + 0] = -R[0][c] - R[1][c];
                 G[c * 3 + 1] = R[0][c];
@@ -117,11 +137,22 @@ void ElasticSolver::add_elements(int kind, int material, const double* verts3, c
             }
         }
         const double w = std::sqrt(k * vol);
-        if (!(w > 0.0)) throw Error(ERR_NUMERIC, "**EnergyTerm::get_reduction Error: Some weight leq 0");
+        if (!(w > 0.0)) throw Error(ERR_NUMERIC, at("**EnergyTerm::get_reduction Error: Some weight leq 0", t));
         g.vol[t] = vol;
         g.w[t] = w;
     }
     hgroups_.push_back(std::move(g));
+}
+
+void ElasticSolver::HostGroup::append_element(const HostGroup& from, size_t t) {
+    idx.insert(idx.end(), from.idx.begin() + t * nv, from.idx.begin() + (t + 1) * nv);
+    G.insert(G.end(), from.G.begin() + t * ncol * nv, from.G.begin() + (t + 1) * ncol * nv);
+    vol.push_back(from.vol[t]);
+    w.push_back(from.w[t]);
+    if (from.per_element()) {
+        mu_e.push_back(from.mu_e[t]); lambda_e.push_back(from.lambda_e[t]); k_e.push_back(from.k_e[t]);
+        if (!from.lmin_e.empty()) { lmin_e.push_back(from.lmin_e[t]); lmax_e.push_back(from.lmax_e[t]); }
+    }
 }
 
 // Solver::add_obstacle (admm_anderson_hard_zxu/src/Solver.cpp:346-348) with the passive objects of
@@ -478,10 +509,7 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
                 if (o < 0) o = (int)(rr++ % P);
                 ++c[o];
                 if (o != rank_) continue;
-                lg.idx.insert(lg.idx.end(), hg.idx.begin() + (size_t)t * hg.nv, hg.idx.begin() + (size_t)(t + 1) * hg.nv);
-                lg.G.insert(lg.G.end(), hg.G.begin() + (size_t)t * hg.ncol * hg.nv, hg.G.begin() + (size_t)(t + 1) * hg.ncol * hg.nv);
-                lg.vol.push_back(hg.vol[t]);
-                lg.w.push_back(hg.w[t]);
+                lg.append_element(hg, (size_t)t);   // the per-element materials travel with the element
             }
             for (int r = 0; r < P; ++r) { br[r] += blocks_for(c[r]); zr[r] += 3LL * hg.ncol * c[r]; }
             owned.push_back(std::move(lg));
@@ -523,6 +551,16 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
         d.idx = dg.idx.p; d.G = dg.G.p; d.w = dg.w.p; d.vol = dg.vol.p;
         d.mu = hg.lame.mu; d.lambda = hg.lame.lambda; d.k = hg.lame.lambda + (2.0 / 3.0) * hg.lame.mu;
         d.lmin = hg.lame.limit_min; d.lmax = hg.lame.limit_max;
+        dg.var = GroupVar{};
+        // (a per-element group of which this rank owns no element stays uniform: nothing launches for it)
+        if (hg.per_element()) {
+            dg.mu_e.upload(hg.mu_e, s()); dg.lambda_e.upload(hg.lambda_e, s()); dg.k_e.upload(hg.k_e, s());
+            dg.var.mu = dg.mu_e.p; dg.var.lambda = dg.lambda_e.p; dg.var.k = dg.k_e.p;
+            if (!hg.lmin_e.empty()) {
+                dg.lmin_e.upload(hg.lmin_e, s()); dg.lmax_e.upload(hg.lmax_e, s());
+                dg.var.lmin = dg.lmin_e.p; dg.var.lmax = dg.lmax_e.p;
+            }
+        }
         if (hg.kind == 2) {   // the obstacle table the collision prox reads (fixed address: graph-safe)
             if (!obs_dev_.p) obs_dev_.alloc(1 + (size_t)kObsStride * kMaxObstacles);
             d.obs = obs_dev_.p;
@@ -670,6 +708,7 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     for (auto& g : groups_) {
         const double per = 4.0 * g.d.nv + 8.0 * g.d.ncol * g.d.nv + 8.0;
         lz += g.d.count * (per + 2 * 8.0 * g.d.dim + 28.0 * g.d.nv);   // u in, z out, slot positions + slots out
+        if (g.var) lz += g.d.count * (g.d.kind == 1 ? 16.0 : g.d.mat != 0 ? 24.0 : 0.0);   // per-element materials
         rs += g.d.count * (per + 3 * 8.0 * g.d.dim);
     }
     kstats_["local_z"].bytes = lz + 24.0 * n;
@@ -752,7 +791,7 @@ void ElasticSolver::local_z_all(const double* xfull, const double* u, double* z,
     if (timed) ev_begin("local_z");
     for (auto& g : groups_) {
         launch_local_z(g.d, xfull, u, z, y, nf_, st_.variant, mode, ctrl_.p, red ? pa_ : nullptr, off, s(),
-                       use_queue_ ? &lq_ : nullptr);
+                       use_queue_ ? &lq_ : nullptr, g.var);
         off += blocks_for(g.d.count);
     }
     if (timed) ev_end("local_z");
@@ -762,7 +801,8 @@ void ElasticSolver::local_z_all(const double* xfull, const double* u, double* z,
 void ElasticSolver::local_z_on(const double* xfull, const double* u, double* z, int mode, hipStream_t st, Ctrl* c,
                                const LocalQueue* q) {
     for (auto& g : groups_)
-        launch_local_z(g.d, xfull, u, z, nullptr, nf_, st_.variant, mode, c, nullptr, 0, st, use_queue_ ? q : nullptr);
+        launch_local_z(g.d, xfull, u, z, nullptr, nf_, st_.variant, mode, c, nullptr, 0, st, use_queue_ ? q : nullptr,
+                       g.var);
 }
 
 void ElasticSolver::prologue() {
@@ -807,7 +847,7 @@ void ElasticSolver::prologue() {
             launch_copy(aa_cur_.p + Z_, xfull_.p, nx, nullptr, 0, s());
         }
     } else {
-        for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u_.p, y_.p, nf_, 2, 0, ctrl_.p, s());
+        for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u_.p, y_.p, nf_, 2, 0, ctrl_.p, s(), g.var);
         launch_rhs(nf_, dt_ptr_.p, nullptr, nullptr, y_.p, Mxbar_.p, pdt2_, b_.p, nullptr, 0, s());
         solver_.solve(b_.p, xfull_.p, nullptr, 0, s());
         local_z_all(xfull_.p, u_.p, z_.p, nullptr, LZ_INIT, false);
@@ -913,7 +953,7 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
         join_wait_ = sst != s();
     };
     ev_begin("grad");
-    for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u_.p, y_.p, nf_, accel ? 1 : 0, 0, c, s());
+    for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u_.p, y_.p, nf_, accel ? 1 : 0, 0, c, s(), g.var);
     ev_end("grad");
     ev_begin("rhs");
     launch_rhs(nf_, dt_ptr_.p, nullptr, nullptr, y_.p, Mxbar_.p, pdt2_, b_.p, c, 0, s());
@@ -953,7 +993,7 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
     if (accel) {   // reject branch (gated on the device; a no-op unless prim increased)
         ev_begin("reject");
         // accelerator.replace(curr_z): the accelerator's iterate is z_ (restored above)
-        for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u_.p, y_.p, nf_, 0, 1, c, s());
+        for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u_.p, y_.p, nf_, 0, 1, c, s(), g.var);
         launch_rhs(nf_, dt_ptr_.p, nullptr, nullptr, y_.p, Mxbar_.p, pdt2_, b_.p, c, 1, s());
         solver_.solve(b_.p, xfull_.p, c, 1, s());
         prim_all(xfull_.p, z_.p, nullptr, 1);

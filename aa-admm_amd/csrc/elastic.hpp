@@ -26,8 +26,9 @@ public:
     ~ElasticSolver();
 
     int add_nodes(const double* x3, const double* m3, int n);
+    // per_element given: [count] Lame parameters, one per element (aa_elastic_add_*_var); `lame` is then unused
     void add_elements(int kind, int material, const double* verts3, const int* idx, int count, const aa_lame& lame,
-                      int vertex_offset);
+                      int vertex_offset, const aa_lame* per_element = nullptr);
     void set_pins(const int* inds, const double* pts3, int n);
     // energy-based collisions of the (u,x) variant (admm_anderson_hard_zxu Solver.cpp:318-348)
     void add_obstacle(int type, const double* params);
@@ -66,11 +67,18 @@ private:
         std::vector<int> idx;       // [count][nv] global node ids
         std::vector<double> G;      // [count][ncol][nv]
         std::vector<double> vol, w;
+        // per-element materials ([count] each; empty = uniform, `lame` holds): k_e = lambda_e + (2/3) mu_e
+        std::vector<double> mu_e, lambda_e, k_e, lmin_e, lmax_e;
+        bool per_element() const { return !k_e.empty(); }
+        // element t of `from` appended (the partitioned solver's split by owner)
+        void append_element(const HostGroup& from, size_t t);
     };
     struct DevGroup {
         DevBuf<int> idx, spos;
         DevBuf<double> G, w, vol;
+        DevBuf<double> mu_e, lambda_e, k_e, lmin_e, lmax_e;
         GroupDev d{};
+        GroupVar var{};   // the arrays above; all null for a uniform group
     };
     Context* ctx_;
     hipStream_t s() const { return ctx_->stream; }

@@ -202,12 +202,29 @@ __device__ __forceinline__ void load_u(const GroupDev& g, int e, const double* _
     }
 }
 
+// ------------------------------------------------------------------ per-element materials
+// The kernels that read material parameters end in a parameter pack: empty for a uniform group
+// (GroupDev's scalars; no argument is added, so those instantiations' code is what it was before
+// the arrays existed), one GroupVar for a group with per-element arrays.
+template <class... V>
+constexpr bool kVar = sizeof...(V) != 0;
+__device__ __forceinline__ const GroupVar& var_of(const GroupVar& v) { return v; }
+// a lane's live (mu, lambda, k) in the work-queue kernels of a per-element group: the values of
+// the element the lane holds, set at the refill (a uniform group reads GroupDev's scalars)
+template <bool VAR>
+struct LaneMat {};
+template <>
+struct LaneMat<true> {
+    double mu = 0, lambda = 0, k = 0;
+};
+
 // ------------------------------------------------------------------ local step
-template <int NV, int HYPER>
+template <int NV, int HYPER, class... V>
 __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __restrict__ xfull,
                                                     const double* __restrict__ u, double* __restrict__ z,
                                                     double* __restrict__ y, int nf, int variant, int mode, Ctrl* ctrl,
-                                                    double* red, int red_off) {
+                                                    double* red, int red_off, V... gvp) {
+    constexpr bool VAR = kVar<V...>;
     if (mode != LZ_INIT && gated(ctrl, mode == LZ_REDO)) return;
     __shared__ double sm[kBlock / 64];
     constexpr int NC = ncol_of(NV), D = 3 * NC;
@@ -227,14 +244,20 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
             if (variant == 1) dev::collision_candidate(F, uu, w, vin);
             dev::collision_prox(vin, g.obs, zz);
         } else if constexpr (NV == 3) {
-            dev::tri_prox(vin, zz, variant, g.lmin, g.lmax);
+            if constexpr (VAR) dev::tri_prox(vin, zz, variant, var_of(gvp...).lmin[e], var_of(gvp...).lmax[e]);
+            else dev::tri_prox(vin, zz, variant, g.lmin, g.lmax);
         } else if constexpr (HYPER == 0) {
             dev::tet_linear_prox(vin, zz);
         } else {
 #pragma unroll
             for (int i = 0; i < D; ++i) zz[i] = vin[i];
             int fail = 0;
-            dev::hyper_prox(g.mat, g.mu, g.lambda, g.k, g.vol[e], vin, zz, &fail);
+            if constexpr (VAR) {
+                const GroupVar& gv = var_of(gvp...);
+                dev::hyper_prox(g.mat, gv.mu[e], gv.lambda[e], gv.k[e], g.vol[e], vin, zz, &fail);
+            } else {
+                dev::hyper_prox(g.mat, g.mu, g.lambda, g.k, g.vol[e], vin, zz, &fail);
+            }
             if (fail && ctrl) ctrl->fail = 1;
         }
 #pragma unroll
@@ -286,12 +309,13 @@ __device__ __forceinline__ int queue_claim(int* queue, int n) {
 // nodes use it (their Cp needs the finished element's positions), as do AA_LQ_FUSED=0 and
 // AA_LQ_FUSED_CONC=0; every other queue launch is k_local_z_hqf below, whose bit-identity
 // baseline this kernel is.
-template <int NV>
+template <int NV, class... V>
 __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double* __restrict__ xfull,
                                                        const double* __restrict__ u, double* __restrict__ z,
                                                        double* __restrict__ y, int nf, int mode, Ctrl* ctrl,
                                                        int* __restrict__ queue, int refill,
-                                                       unsigned long long* __restrict__ stats) {
+                                                       unsigned long long* __restrict__ stats, V... gvp) {
+    constexpr bool VAR = kVar<V...>;
     if (mode != LZ_INIT && gated(ctrl, mode == LZ_REDO)) return;
     unsigned trips = 0, refills = 0;
     __shared__ unsigned hist[101];   // diagnostics only: per-block histogram, flushed at the end
@@ -302,6 +326,7 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
     constexpr int D = 3 * (NV - 1);
     const int lane = threadIdx.x & 63;
     dev::HyperLbfgs L;
+    [[maybe_unused]] LaneMat<VAR> M;
     double v[D], x[D];
     double vol = 0;
     int e = -1, fail = 0;
@@ -354,7 +379,15 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
                         x[i] = v[i];
                     }
                     vol = g.vol[e];
-                    if (L.start(g.mat, g.mu, g.lambda, g.k, vol, v, x)) {
+                    bool ok;
+                    if constexpr (VAR) {
+                        const GroupVar& gv = var_of(gvp...);
+                        M.mu = gv.mu[e]; M.lambda = gv.lambda[e]; M.k = gv.k[e];
+                        ok = L.start(g.mat, M.mu, M.lambda, M.k, vol, v, x);
+                    } else {
+                        ok = L.start(g.mat, g.mu, g.lambda, g.k, vol, v, x);
+                    }
+                    if (ok) {
                         finalize();
                         if (stats) atomicAdd(&hist[0], 1u);
                     } else {
@@ -363,7 +396,10 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
                 }
             }
         }
-        if (active && L.iterate(g.mat, g.mu, g.lambda, g.k, vol, v, x, &fail)) {
+        bool fin = false;
+        if constexpr (VAR) fin = active && L.iterate(g.mat, M.mu, M.lambda, M.k, vol, v, x, &fail);
+        else fin = active && L.iterate(g.mat, g.mu, g.lambda, g.k, vol, v, x, &fail);
+        if (fin) {
             active = false;
             pending = true;
             if (stats) atomicAdd(&hist[min(L.k_it, 100)], 1u);
@@ -399,12 +435,13 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
 // combined-residual pass writes no slots and runs SLOTS = false: without the slot loads it holds
 // 412 registers, which do leave that room (ElasticSolver::initialize). C4 (same box, two A/B
 // pairs): local_z 433 / 435 -> 422 / 418 us.
-template <int NV, bool SLOTS = true>
+template <int NV, bool SLOTS = true, class... V>
 __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double* __restrict__ xfull,
                                                         const double* __restrict__ u, double* __restrict__ z,
                                                         double* __restrict__ y, int nf, int mode, Ctrl* ctrl,
                                                         int* __restrict__ queue, int refill,
-                                                        unsigned long long* __restrict__ stats) {
+                                                        unsigned long long* __restrict__ stats, V... gvp) {
+    constexpr bool VAR = kVar<V...>;
     static_assert(NV == 4, "the fused refill is for tets");
     if (mode != LZ_INIT && gated(ctrl, mode == LZ_REDO)) return;
     unsigned trips = 0, refills = 0;
@@ -416,6 +453,7 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double
     constexpr int NC = ncol_of(NV), D = 3 * NC;
     const int lane = threadIdx.x & 63;
     dev::HyperLbfgs L;
+    [[maybe_unused]] LaneMat<VAR> M;
     double v[D], x[D];
     double vol = 0;
     int e = 0, fail = 0;
@@ -471,6 +509,11 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double
             for (int k = 0; k < NC * NV; ++k) gn[k] = g.G[k * n + en];
             load_u<D>(g, en, u, un);
             const double wn = g.w[en], voln = g.vol[en];
+            [[maybe_unused]] double mun = 0, lamn = 0, kn = 0;   // per-element materials: staged with the group above
+            if constexpr (VAR) {
+                const GroupVar& gv = var_of(gvp...);
+                mun = gv.mu[en]; lamn = gv.lambda[en]; kn = gv.k[en];
+            }
             if (need) {
                 if (my >= g.count) {
                     exhausted = true;
@@ -493,7 +536,14 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double
                         x[i] = v[i];
                     }
                     vol = voln;
-                    if (L.start(g.mat, g.mu, g.lambda, g.k, vol, v, x)) {
+                    bool ok;
+                    if constexpr (VAR) {
+                        M.mu = mun; M.lambda = lamn; M.k = kn;
+                        ok = L.start(g.mat, M.mu, M.lambda, M.k, vol, v, x);
+                    } else {
+                        ok = L.start(g.mat, g.mu, g.lambda, g.k, vol, v, x);
+                    }
+                    if (ok) {
                         pending = true;
                         if (stats) atomicAdd(&hist[0], 1u);
                     } else {
@@ -502,7 +552,10 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double
                 }
             }
         }
-        if (active && L.iterate(g.mat, g.mu, g.lambda, g.k, vol, v, x, &fail)) {
+        bool fin = false;
+        if constexpr (VAR) fin = active && L.iterate(g.mat, M.mu, M.lambda, M.k, vol, v, x, &fail);
+        else fin = active && L.iterate(g.mat, g.mu, g.lambda, g.k, vol, v, x, &fail);
+        if (fin) {
             active = false;
             pending = true;
             if (stats) atomicAdd(&hist[min(L.k_it, 100)], 1u);
@@ -706,10 +759,12 @@ __global__ __launch_bounds__(kBlock) void k_resid_u(GroupDev g, const double* __
 }
 
 // Z variant: u update (mode 0 dual ascent, 1 = W^-1 grad E(z), 2 = keep u) then y = w (w z + c - u)
-template <int NV, int HYPER>
+template <int NV, int HYPER, class... V>
 __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __restrict__ xfull,
                                                     const double* __restrict__ z, double* __restrict__ u,
-                                                    double* __restrict__ y, int nf, int mode, int redo, Ctrl* ctrl) {
+                                                    double* __restrict__ y, int nf, int mode, int redo, Ctrl* ctrl,
+                                                    V... gvp) {
+    constexpr bool VAR = kVar<V...>;
     if (gated(ctrl, redo)) return;
     constexpr int NC = ncol_of(NV), D = 3 * NC;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -720,6 +775,11 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
     const double w = g.w[e];
     // the element volume with the other loads (loaded where it is used, it waited alone mid-gradient)
     const double vol = (NV == 4 && mode == 1) ? g.vol[e] : 0.0;
+    double mu = g.mu, lambda = g.lambda, k = g.k;
+    if constexpr (VAR && NV == 4) {
+        const GroupVar& gv = var_of(gvp...);
+        if (mode == 1) { mu = gv.mu[e]; lambda = gv.lambda[e]; k = gv.k[e]; }
+    }
 #pragma unroll
     for (int i = 0; i < D; ++i) zz[i] = z[g.zoff + (size_t)i * g.count + e];
     if (mode != 1) {
@@ -734,9 +794,9 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
 #pragma unroll
             for (int i = 0; i < D; ++i) gr[i] = 0;
         } else if constexpr (HYPER == 0) {
-            dev::tet_linear_grad(zz, g.k * vol, gr);
+            dev::tet_linear_grad(zz, k * vol, gr);
         } else {
-            dev::hyper_psi_grad(g.mat, g.mu, g.lambda, zz, gr);
+            dev::hyper_psi_grad(g.mat, mu, lambda, zz, gr);
 #pragma unroll
             for (int i = 0; i < D; ++i) gr[i] *= vol;
         }
@@ -1670,23 +1730,38 @@ LocalQueue make_local_queue(int device, int* counter) {
     AA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kq, kBlock, 0));
     q.resident = std::max(1, cus * std::max(1, per));
     q.refill = r ? std::atoi(r) : 60;
+    q.refill_lanes = q.refill;
     if (q.split) q.refill = std::max(1, (q.refill + 1) / 2);   // in pairs (elements) per wave
     return q;
 }
 
 void launch_local_z(const GroupDev& g, const double* xfull, const double* u, double* z, double* y, int nf,
-                    int variant, int mode, Ctrl* ctrl, double* red, int red_off, hipStream_t s, const LocalQueue* queue) {
+                    int variant, int mode, Ctrl* ctrl, double* red, int red_off, hipStream_t s, const LocalQueue* queue,
+                    const GroupVar& var) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
     if (g.kind == 0 && g.mat != 0 && !red && queue && queue->counter) {   // hyperelastic, no partials: work queue
-        // k_local_z_hq / k_local_z_hqf reset the queue themselves (queue_reset_last); k_local_z_hq2 does not
-        if (queue->split) AA_HIP(hipMemsetAsync(queue->counter, 0, sizeof(int), s));
+        // k_local_z_hq / k_local_z_hqf reset the queue themselves (queue_reset_last); k_local_z_hq2 does not.
+        // A per-element group never takes k_local_z_hq2: AA_LQ_SPLIT is ignored for it.
+        const bool split = queue->split && !var;
+        if (split) AA_HIP(hipMemsetAsync(queue->counter, 0, sizeof(int), s));
         const int resident = std::max(1, queue->resident), refill = queue->refill;
         const dim3 grid(std::min(nb, resident));
-        if (queue->split) {   // two lanes per element: half the elements per block
+        if (split) {   // two lanes per element: half the elements per block
             const dim3 grid2(std::min(blocks_for(2LL * g.count), resident));
             hipLaunchKernelGGL((k_local_z_hq2<4>), grid2, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode, ctrl,
                                queue->counter, refill, queue->stats);
+        } else if (var) {
+            const int rf = queue->refill_lanes;
+            if (!queue->fused || g.pinned)
+                hipLaunchKernelGGL((k_local_z_hq<4, GroupVar>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode, ctrl,
+                                   queue->counter, rf, queue->stats, var);
+            else if (y)
+                hipLaunchKernelGGL((k_local_z_hqf<4, true, GroupVar>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode,
+                                   ctrl, queue->counter, rf, queue->stats, var);
+            else
+                hipLaunchKernelGGL((k_local_z_hqf<4, false, GroupVar>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf,
+                                   mode, ctrl, queue->counter, rf, queue->stats, var);
         } else if (!queue->fused || g.pinned)   // pinned groups keep the plain refill (their Cp needs positions)
             hipLaunchKernelGGL((k_local_z_hq<4>), grid, dim3(kBlock), 0, s, g, xfull, u, z, y, nf, mode, ctrl,
                                queue->counter, refill, queue->stats);
@@ -1700,8 +1775,10 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
         return;
     }
     if (g.kind == 2) hipLaunchKernelGGL((k_local_z<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+    else if (g.kind == 1 && var) hipLaunchKernelGGL((k_local_z<3, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, var);
     else if (g.kind == 1) hipLaunchKernelGGL((k_local_z<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
-    else if (g.mat == 0) hipLaunchKernelGGL((k_local_z<4, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+    else if (g.mat == 0) hipLaunchKernelGGL((k_local_z<4, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);   // the linear prox reads w only
+    else if (var) hipLaunchKernelGGL((k_local_z<4, 1, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, var);
     else hipLaunchKernelGGL((k_local_z<4, 1>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
     AA_CHECK_LAUNCH();
 }
@@ -1717,12 +1794,14 @@ void launch_resid_update_u(const GroupDev& g, const double* xfull, const double*
 }
 
 void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, double* u, double* y, int nf, int mode,
-                    int redo, Ctrl* ctrl, hipStream_t s) {
+                    int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
     if (g.kind == 2) hipLaunchKernelGGL((k_u_and_y<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl);
-    else if (g.kind == 1) hipLaunchKernelGGL((k_u_and_y<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl);
+    else if (g.kind == 1) hipLaunchKernelGGL((k_u_and_y<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl);   // no material reads
+    else if (g.mat == 0 && var) hipLaunchKernelGGL((k_u_and_y<4, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl, var);
     else if (g.mat == 0) hipLaunchKernelGGL((k_u_and_y<4, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl);
+    else if (var) hipLaunchKernelGGL((k_u_and_y<4, 1, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl, var);
     else hipLaunchKernelGGL((k_u_and_y<4, 1>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl);
     AA_CHECK_LAUNCH();
 }

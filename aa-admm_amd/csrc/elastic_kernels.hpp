@@ -24,6 +24,20 @@ struct GroupDev {
     double mu, lambda, k, lmin, lmax;
     const double* obs;   // collision points: the obstacle table (obs[0] = count, then kObsStride per obstacle)
 };
+// Per-element material parameters of a group (aa_elastic_add_*_var; the reference's one Lame per
+// EnergyTerm, TetEnergyTerm.hpp:36-51 / TriEnergyTerm.hpp:33-47), [count] each like w and vol;
+// all null = a uniform group, whose kernels read GroupDev's scalars. Kept beside GroupDev, not in
+// it, and handed only to the per-element instantiations (as their last argument): GroupDev is the
+// first argument of every element kernel, so growing it would move every uniform kernel's
+// arguments. k = lambda + (2/3) mu is formed on the host with the uniform path's expression.
+struct GroupVar {
+    const double* mu = nullptr;
+    const double* lambda = nullptr;
+    const double* k = nullptr;
+    const double* lmin = nullptr;    // triangles only
+    const double* lmax = nullptr;
+    explicit operator bool() const { return k != nullptr; }
+};
 // passive obstacles of the collision terms (PassiveObject.hpp:32-136): type, then up to 7 parameters
 enum ObsType { OBS_FLOOR = 0, OBS_SLIDE_FLOOR = 1, OBS_SPHERE = 2, OBS_PLANE_HALF_SPHERE = 3, OBS_CYLINDER = 4 };
 constexpr int kObsStride = 8, kMaxObstacles = 256;
@@ -76,6 +90,7 @@ enum LocalMode { LZ_NORMAL = 0, LZ_REDO = 1, LZ_INIT = 2 };
 struct LocalQueue {
     int* counter = nullptr;
     int resident = 0, refill = 60;
+    int refill_lanes = 60;   // refill before the split queue halves it (per-element groups never split)
     // k_local_z_hqf (the refill's loads regrouped; groups without pins) instead of the plain
     // k_local_z_hq: the default, AA_LQ_FUSED=0 turns it off
     bool fused = false;
@@ -88,15 +103,16 @@ constexpr int kLqStats = 104;
 LocalQueue make_local_queue(int device, int* counter);
 // z = prox(P x + u/w); prim partials; optional y = w(w z + c - u). gate: !done (and reject for REDO)
 // queue given: hyperelastic groups without partials run as a persistent work queue
+// var given (launch_u_and_y too): the group's per-element material instantiation of the same kernel
 void launch_local_z(const GroupDev& g, const double* xfull, const double* u, double* z, double* y, int nf,
                     int variant, int mode, Ctrl* ctrl, double* red, int red_off, hipStream_t s,
-                    const LocalQueue* queue = nullptr);
+                    const LocalQueue* queue = nullptr, const GroupVar& var = GroupVar());
 // r = w(P x - z); prim2/dual2 partials; u += r (UX variant update_u fused with the residual)
 void launch_resid_update_u(const GroupDev& g, const double* xfull, const double* xlast, const double* z, double* u,
                            int nf, Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s);
 // Z variant: u += w(Px - z) [mode 0] or u = grad E(z)/w [mode 1]; then y = w(w z + c - u). gate !done (+reject if redo)
 void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, double* u, double* y, int nf, int mode,
-                    int redo, Ctrl* ctrl, hipStream_t s);
+                    int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var = GroupVar());
 // prim2 partials of |w(Px - z)|^2 and optionally dual2 partials of |w(z - zref)|^2. gate !done (+reject if redo)
 void launch_prim_z(const GroupDev& g, const double* xfull, const double* z, const double* zref, int nf, int redo,
                    Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s);

@@ -48,11 +48,26 @@ def lame(E: float, nu: float):
 class ElementGroup:
     kind: int             # TET or TRI
     material: int         # LINEAR / NEOHOOKEAN / STVK (tets); LINEAR for tris
-    E: float
-    nu: float
+    E: float              # E, nu, limit_min, limit_max: scalars, or arrays of the group's length
+    nu: float             # (per-element materials: the reference's one Lame per EnergyTerm)
     idx: np.ndarray       # int32 (count, 4) or (count, 3)
     limit_min: float = -100.0   # Lame defaults (EnergyTerm.hpp:54-55)
     limit_max: float = 100.0
+
+    @property
+    def per_element(self) -> bool:
+        return any(np.ndim(a) > 0 for a in (self.E, self.nu, self.limit_min, self.limit_max))
+
+    def material_arrays(self):
+        """E, nu, limit_min, limit_max as fp64 arrays of the group's length (scalars broadcast)."""
+        n = len(self.idx)
+        out = []
+        for a in (self.E, self.nu, self.limit_min, self.limit_max):
+            a = np.asarray(a, np.float64)
+            if a.ndim > 0 and a.shape != (n,):
+                raise ValueError(f"per-element material array of shape {a.shape} for a group of {n} elements")
+            out.append(np.broadcast_to(a, (n,)).copy())
+        return out
 
 
 @dataclasses.dataclass
@@ -90,6 +105,38 @@ class Scene:
 
     def n_elements(self) -> int:
         return int(sum(len(g.idx) for g in self.groups))
+
+
+def per_element_groups(scene: Scene) -> Scene:
+    """The equivalent scene with one one-element scalar group per element, in element order: the
+    reference's layout (one EnergyTerm per element, each with its own Lame), which the reference
+    driver and the oracle read. Uniform groups are expanded the same way."""
+    groups = []
+    for g in scene.groups:
+        E, nu, lmin, lmax = g.material_arrays()
+        idx = np.asarray(g.idx, np.int32)
+        for e in range(len(idx)):
+            groups.append(ElementGroup(g.kind, g.material, float(E[e]), float(nu[e]), idx[e:e + 1].copy(),
+                                       float(lmin[e]), float(lmax[e])))
+    return dataclasses.replace(scene, groups=groups)
+
+
+def with_material_levels(scene: Scene, E_levels, nu_levels, lmin_levels=None, lmax_levels=None, seed=7) -> Scene:
+    """The scene (a single group) with a random material level per element: level
+    np.random.default_rng(seed).integers(0, L, n) of the given tables, as per-element arrays."""
+    if len(scene.groups) != 1:
+        raise ValueError("with_material_levels: the scene must have a single group")
+    g = scene.groups[0]
+    E_levels, nu_levels = np.asarray(E_levels, np.float64), np.asarray(nu_levels, np.float64)
+    L = len(E_levels)
+    if len(nu_levels) != L or any(t is not None and len(t) != L for t in (lmin_levels, lmax_levels)):
+        raise ValueError("with_material_levels: the level tables must have one length")
+    lvl = np.random.default_rng(seed).integers(0, L, len(g.idx))
+    new = dataclasses.replace(
+        g, E=E_levels[lvl], nu=nu_levels[lvl],
+        limit_min=g.limit_min if lmin_levels is None else np.asarray(lmin_levels, np.float64)[lvl],
+        limit_max=g.limit_max if lmax_levels is None else np.asarray(lmax_levels, np.float64)[lvl])
+    return dataclasses.replace(scene, groups=[new])
 
 
 # ----------------------------------------------------------------------------------------

@@ -102,6 +102,18 @@ int aa_elastic_add_tets(aa_elastic h, const double* verts3, const int* tets4, in
 /* create_tris_from_mesh<IN_SCALAR,TriEnergyTerm> (TriEnergyTerm.hpp:33-47). */
 int aa_elastic_add_tris(aa_elastic h, const double* verts3, const int* tris3, int n_tris, const aa_lame* lame,
                         int vertex_offset);
+/* Per-element materials: the reference builds one EnergyTerm per tet / triangle and each term owns
+ * its Lame (TetEnergyTerm.hpp:36-51, TriEnergyTerm.hpp:33-47), so a caller may loop over the elements
+ * with a stiffness that varies in space. These calls take that loop as one group (one launch per kernel
+ * class, one work queue): the semantics of n create_*_from_mesh calls of one element each, in element
+ * order, with lame_per_*[e]. `material` stays per call; mu and lambda (and, for triangles, the strain
+ * limits) vary. The scalar calls' errors apply per element with the same codes and messages, which
+ * also name the first offending element; a null array with n > 0 or a non-finite mu / lambda is
+ * AA_ERR_ARG. */
+int aa_elastic_add_tets_var(aa_elastic h, const double* verts3, const int* tets4, int n_tets, int material,
+                            const aa_lame* lame_per_tet /* [n_tets] */, int vertex_offset);
+int aa_elastic_add_tris_var(aa_elastic h, const double* verts3, const int* tris3, int n_tris,
+                            const aa_lame* lame_per_tri /* [n_tris] */, int vertex_offset);
 /* Solver::set_pins(inds, points): points3 == NULL pins in place (Solver.cpp:280-315). */
 int aa_elastic_set_pins(aa_elastic h, const int* inds, const double* points3, int n_pins);
 

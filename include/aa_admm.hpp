@@ -55,6 +55,7 @@ public:
     virtual ~EnergyTerm() {}
     int kind = 0, material = AA_LINEAR;   // kind 0 tet, 1 tri
     Lame lame;
+    std::vector<Lame> lames;     // per-element materials ([count]); empty: `lame` for every element
     std::vector<double> verts;   // rest shape (as given to create_*_from_mesh)
     std::vector<int> inds;
     int count = 0, vertex_offset = 0;
@@ -96,6 +97,24 @@ inline void create_tris_from_mesh(std::vector<std::shared_ptr<EnergyTerm>>& ener
     e->count = n_tris;
     e->vertex_offset = vertex_offset;
     energyterms.push_back(e);
+}
+
+// Per-element materials: lames[e] is element e's Lame -- the reference caller's loop of one-element
+// create_*_from_mesh calls (each EnergyTerm owns its Lame, TetEnergyTerm.hpp:36-51 /
+// TriEnergyTerm.hpp:33-47) as one descriptor and one device group.
+template <typename IN_SCALAR, typename TYPE>
+inline void create_tets_from_mesh(std::vector<std::shared_ptr<EnergyTerm>>& energyterms, const IN_SCALAR* verts,
+                                  const int* inds, int n_tets, const std::vector<Lame>& lames, const int vertex_offset) {
+    if ((int)lames.size() != n_tets) throw std::runtime_error("create_tets_from_mesh: one Lame per tet expected");
+    create_tets_from_mesh<IN_SCALAR, TYPE>(energyterms, verts, inds, n_tets, Lame(), vertex_offset);
+    energyterms.back()->lames = lames;
+}
+template <typename IN_SCALAR, typename TYPE>
+inline void create_tris_from_mesh(std::vector<std::shared_ptr<EnergyTerm>>& energyterms, const IN_SCALAR* verts,
+                                  const int* inds, int n_tris, const std::vector<Lame>& lames, const int vertex_offset) {
+    if ((int)lames.size() != n_tris) throw std::runtime_error("create_tris_from_mesh: one Lame per triangle expected");
+    create_tris_from_mesh<IN_SCALAR, TYPE>(energyterms, verts, inds, n_tris, Lame(), vertex_offset);
+    energyterms.back()->lames = lames;
 }
 
 typedef std::array<double, 3> Vec3d;
@@ -223,9 +242,18 @@ public:
             if (aa_elastic_add_nodes(h_, m_x.data(), m_masses.data(), (int)m_x.size() / 3, &total) != AA_OK) return false;
             for (auto& e : energyterms) {
                 aa_lame l = e->lame.c();
-                const int rc = e->kind == 0
-                    ? aa_elastic_add_tets(h_, e->verts.data(), e->inds.data(), e->count, e->material, &l, e->vertex_offset)
-                    : aa_elastic_add_tris(h_, e->verts.data(), e->inds.data(), e->count, &l, e->vertex_offset);
+                int rc;
+                if (!e->lames.empty()) {   // per-element materials: the _var calls
+                    std::vector<aa_lame> ls;
+                    for (auto& le : e->lames) ls.push_back(le.c());
+                    rc = e->kind == 0
+                        ? aa_elastic_add_tets_var(h_, e->verts.data(), e->inds.data(), e->count, e->material, ls.data(), e->vertex_offset)
+                        : aa_elastic_add_tris_var(h_, e->verts.data(), e->inds.data(), e->count, ls.data(), e->vertex_offset);
+                } else {
+                    rc = e->kind == 0
+                        ? aa_elastic_add_tets(h_, e->verts.data(), e->inds.data(), e->count, e->material, &l, e->vertex_offset)
+                        : aa_elastic_add_tris(h_, e->verts.data(), e->inds.data(), e->count, &l, e->vertex_offset);
+                }
                 if (rc != AA_OK) return false;
             }
             bound_ = true;
