@@ -476,6 +476,10 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     conc_ = pipe_z_ && !comm_;
     if (const char* e = std::getenv("AA_CONCURRENT")) conc_ = conc_ && e[0] != '0';
     conc_fork_ = std::getenv("AA_CONC_FORK") ? std::atoi(std::getenv("AA_CONC_FORK")) : 1;
+    // u in the parity buffers of the concurrent pass (elastic.hpp); AA_Z_WINDOW=0: u in u_, copied
+    // to default_u in the window and restored from it on a reject
+    win_u_ = conc_;
+    if (const char* e = std::getenv("AA_Z_WINDOW")) win_u_ = win_u_ && e[0] != '0';
     // Z variant + Anderson: the two-set layout whether pipelined or not (same sums, same bits)
     stamp("factor");
     // the sweeps as two parallel branches (DirectSolver::plan_branches): measured on C4 (one GPU,
@@ -617,7 +621,7 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     xfull_.zero(s()); xlast_.zero(s()); cxfull_.zero(s());
     xbar_.alloc(3 * (size_t)nf_); Mxbar_.alloc(3 * (size_t)nf_); b_.alloc(3 * (size_t)nf_);
     if (pipe_z_) b2_.alloc(3 * (size_t)nf_); dx_.alloc(3 * (size_t)nf_);
-    z_.alloc(Z_); u_.alloc(Z_); y_.alloc(3 * std::max<long long>(1, Yslots_)); du_.alloc(Z_);
+    z_.alloc(Z_); if (!win_u_) u_.alloc(Z_); y_.alloc(3 * std::max<long long>(1, Yslots_)); du_.alloc(Z_);
     if (st_.variant == AA_VARIANT_Z) { dz_.alloc(Z_); lastz_.alloc(Z_); cz_.alloc(Z_); }
     if (conc_) {
         du2_.alloc(Z_); dz2_.alloc(Z_); dx2_.alloc(3 * (size_t)nf_);
@@ -827,7 +831,9 @@ void ElasticSolver::prologue() {
     if (comm_ && rank_ != 0 && top_beg_ < nf_)
         AA_HIP(hipMemsetAsync(Mxbar_.p + 3 * (size_t)top_beg_, 0, 3 * sizeof(double) * (size_t)(nf_ - top_beg_), s()));
     for (auto& g : groups_) launch_init_z(g.d, xfull_.p, z_.p, s());
-    u_.zero(s());
+    // u = 0 (win_u_: in default_u of "iteration -1", where iteration 0's reject branch reads it)
+    double* u0 = u_at(-1);
+    if (Z_) AA_HIP(hipMemsetAsync(u0, 0, sizeof(double) * (size_t)Z_, s()));
     const long long nx = 3LL * nf_;
     if (st_.variant == AA_VARIANT_UX) {
         local_z_all(xfull_.p, u_.p, z_.p, y_.p, LZ_INIT, false);
@@ -847,14 +853,14 @@ void ElasticSolver::prologue() {
             launch_copy(aa_cur_.p + Z_, xfull_.p, nx, nullptr, 0, s());
         }
     } else {
-        for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u_.p, y_.p, nf_, 2, 0, ctrl_.p, s(), g.var);
+        for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u0, u0, y_.p, nf_, 2, 0, ctrl_.p, s(), g.var);
         launch_rhs(nf_, dt_ptr_.p, nullptr, nullptr, y_.p, Mxbar_.p, pdt2_, b_.p, nullptr, 0, s());
         solver_.solve(b_.p, xfull_.p, nullptr, 0, s());
-        local_z_all(xfull_.p, u_.p, z_.p, nullptr, LZ_INIT, false);
+        local_z_all(xfull_.p, u0, z_.p, nullptr, LZ_INIT, false);
         // default_{z,x,u} of "iteration -1" (the parity buffers of the concurrent pass)
         launch_copy(dz_at(-1), z_.p, Z_, nullptr, 0, s());
         launch_copy(dx_at(-1), xfull_.p, nx, nullptr, 0, s());
-        launch_copy(du_at(-1), u_.p, Z_, nullptr, 0, s());
+        if (!win_u_) launch_copy(du_at(-1), u_.p, Z_, nullptr, 0, s());
         // (Z variant: the accelerator's current iterate is z_ itself)
     }
 }
@@ -952,8 +958,15 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
         if (sst != s()) AA_HIP(hipEventRecord(ev_join_, sst));
         join_wait_ = sst != s();
     };
+    // the working u: u_, or (win_u_) this iteration's default_u buffer itself. Nothing else touches
+    // that buffer while this iteration uses it: the pass of iteration it - 2, the last reader of
+    // what it held, was joined at the end of iteration it - 1. ui: what the reject branch's dual
+    // ascent starts from, default_u of the previous iteration -- restored into u_ by
+    // k_check_restore_z, or read where it lies
+    double* u = u_at(it);
+    const double* ui = win_u_ ? dup : u_.p;
     ev_begin("grad");
-    for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u_.p, y_.p, nf_, accel ? 1 : 0, 0, c, s(), g.var);
+    for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u, u, y_.p, nf_, accel ? 1 : 0, 0, c, s(), g.var);
     ev_end("grad");
     ev_begin("rhs");
     launch_rhs(nf_, dt_ptr_.p, nullptr, nullptr, y_.p, Mxbar_.p, pdt2_, b_.p, c, 0, s());
@@ -989,11 +1002,11 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
     reduce_partials();
     // the reject test with the restore of the defaults fused (gated on the device: copies only
     // when prim increased)
-    launch_check_restore_z(c, ga_, nbg_, accel, u_.p, xfull_.p, z_.p, dup, dxp, dzp, Z_, nx, s());
+    launch_check_restore_z(c, ga_, nbg_, accel, win_u_ ? nullptr : u_.p, xfull_.p, z_.p, dup, dxp, dzp, Z_, nx, s());
     if (accel) {   // reject branch (gated on the device; a no-op unless prim increased)
         ev_begin("reject");
         // accelerator.replace(curr_z): the accelerator's iterate is z_ (restored above)
-        for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, u_.p, y_.p, nf_, 0, 1, c, s(), g.var);
+        for (auto& g : groups_) launch_u_and_y(g.d, xfull_.p, z_.p, ui, u, y_.p, nf_, 0, 1, c, s(), g.var);
         launch_rhs(nf_, dt_ptr_.p, nullptr, nullptr, y_.p, Mxbar_.p, pdt2_, b_.p, c, 1, s());
         solver_.solve(b_.p, xfull_.p, c, 1, s());
         prim_all(xfull_.p, z_.p, nullptr, 1);
@@ -1006,10 +1019,12 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
         // default_x / default_u (Solver.cpp:194-195): nothing reads them before the combined-residual
         // pass, so they are copied after the Anderson reduce, beside the concurrent pass's local
         // step instead of on the critical path (the instrumented pass times them here, on their own)
+        // (win_u_: u is default_u already -- a memory-bound pass beside the local step runs at
+        // half speed, and this one was 2 x 8 Z_ bytes)
         auto copy_defaults = [&]() {
             ev_begin("copy");
             launch_copy(dxc, xfull_.p, nx, c, 0, s());
-            launch_copy(duc, u_.p, Z_, c, 0, s());
+            if (!win_u_) launch_copy(duc, u_.p, Z_, c, 0, s());
             ev_end("copy");
         };
         if (instrument_) copy_defaults();
@@ -1017,7 +1032,7 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
         // rhs slots of the combined-residual solve, w (w default_z + C - curr_u)
         // (Solver.cpp:220): curr_u is final for this iteration and the AA step does not touch it
         ev_begin("local_z");
-        local_z_all(xfull_.p, u_.p, dzc, y_.p, LZ_NORMAL, false);
+        local_z_all(xfull_.p, u, dzc, y_.p, LZ_NORMAL, false);
         ev_end("local_z");
         fork_side(0);
         Seg2 G{dzc, Z_, nullptr, 0};
@@ -1052,7 +1067,7 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
     }
     launch_copy(lastz_.p, z_.p, Z_, c, 0, s());
     ev_begin("local_z");
-    local_z_all(xfull_.p, u_.p, z_.p, nullptr, LZ_NORMAL, false);
+    local_z_all(xfull_.p, u, z_.p, nullptr, LZ_NORMAL, false);
     ev_end("local_z");
     prim_all(xfull_.p, z_.p, lastz_.p, 0);
     reduce_partials();

@@ -169,6 +169,11 @@ private:
     double* du_at(int it) { return conc_ && (it & 1) ? du2_.p : du_.p; }
     double* dz_at(int it) { return conc_ && (it & 1) ? dz2_.p : dz_.p; }
     double* dx_at(int it) { return conc_ && (it & 1) ? dx2_.p : dx_.p; }
+    // win_u_ (with conc_; AA_Z_WINDOW=0 turns it off): iteration `it` keeps its working u in
+    // du_at(it) itself -- no default_u copy in the window beside the pass's local step, no restore
+    // of u on a reject (the reject branch reads du_at(it - 1) where it lies); u_ is then unused
+    bool win_u_ = false;
+    double* u_at(int it) { return win_u_ ? du_at(it) : u_.p; }
 
     // kernel-class event timing (bench only)
     bool instrument_ = false;

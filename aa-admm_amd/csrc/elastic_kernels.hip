@@ -759,9 +759,12 @@ __global__ __launch_bounds__(kBlock) void k_resid_u(GroupDev g, const double* __
 }
 
 // Z variant: u update (mode 0 dual ascent, 1 = W^-1 grad E(z), 2 = keep u) then y = w (w z + c - u)
+// uin: the u that modes 0 and 2 read (mode 1 reads none); u: where modes 0 and 1 write it. The two
+// are the same buffer unless u alternates between the parity buffers of the concurrent pass
+// (ElasticSolver::u_at), so neither is __restrict__; each thread reads its entries before it writes them.
 template <int NV, int HYPER, class... V>
 __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __restrict__ xfull,
-                                                    const double* __restrict__ z, double* __restrict__ u,
+                                                    const double* __restrict__ z, const double* uin, double* u,
                                                     double* __restrict__ y, int nf, int mode, int redo, Ctrl* ctrl,
                                                     V... gvp) {
     constexpr bool VAR = kVar<V...>;
@@ -784,7 +787,7 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
     for (int i = 0; i < D; ++i) zz[i] = z[g.zoff + (size_t)i * g.count + e];
     if (mode != 1) {
 #pragma unroll
-        for (int i = 0; i < D; ++i) uu[i] = u[g.zoff + (size_t)i * g.count + e];
+        for (int i = 0; i < D; ++i) uu[i] = uin[g.zoff + (size_t)i * g.count + e];
     }
     if (mode == 1) {
         double gr[D];
@@ -1106,11 +1109,12 @@ __global__ __launch_bounds__(kCtlBlock) void k_check_restore_z(Ctrl* ctrl, const
     }
     __syncthreads();
     if (!rej) return;
-    const long long n = 2 * nz + nx;
+    // u null: the reject branch reads default_u where it lies (k_u_and_y's uin), nothing to restore
+    const long long nu = u ? nz : 0, n = nu + nx + nz;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        if (i < nz) u[i] = du[i];
-        else if (i < nz + nx) x[i - nz] = dx[i - nz];
-        else z[i - nz - nx] = dz[i - nz - nx];
+        if (i < nu) u[i] = du[i];
+        else if (i < nu + nx) x[i - nu] = dx[i - nu];
+        else z[i - nu - nx] = dz[i - nu - nx];
     }
 }
 
@@ -1793,16 +1797,16 @@ void launch_resid_update_u(const GroupDev& g, const double* xfull, const double*
     AA_CHECK_LAUNCH();
 }
 
-void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, double* u, double* y, int nf, int mode,
-                    int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var) {
+void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, const double* uin, double* u, double* y,
+                    int nf, int mode, int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 2) hipLaunchKernelGGL((k_u_and_y<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl);
-    else if (g.kind == 1) hipLaunchKernelGGL((k_u_and_y<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl);   // no material reads
-    else if (g.mat == 0 && var) hipLaunchKernelGGL((k_u_and_y<4, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl, var);
-    else if (g.mat == 0) hipLaunchKernelGGL((k_u_and_y<4, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl);
-    else if (var) hipLaunchKernelGGL((k_u_and_y<4, 1, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl, var);
-    else hipLaunchKernelGGL((k_u_and_y<4, 1>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, u, y, nf, mode, redo, ctrl);
+    if (g.kind == 2) hipLaunchKernelGGL((k_u_and_y<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+    else if (g.kind == 1) hipLaunchKernelGGL((k_u_and_y<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);   // no material reads
+    else if (g.mat == 0 && var) hipLaunchKernelGGL((k_u_and_y<4, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl, var);
+    else if (g.mat == 0) hipLaunchKernelGGL((k_u_and_y<4, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+    else if (var) hipLaunchKernelGGL((k_u_and_y<4, 1, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl, var);
+    else hipLaunchKernelGGL((k_u_and_y<4, 1>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
     AA_CHECK_LAUNCH();
 }
 

@@ -110,9 +110,10 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
 // r = w(P x - z); prim2/dual2 partials; u += r (UX variant update_u fused with the residual)
 void launch_resid_update_u(const GroupDev& g, const double* xfull, const double* xlast, const double* z, double* u,
                            int nf, Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s);
-// Z variant: u += w(Px - z) [mode 0] or u = grad E(z)/w [mode 1]; then y = w(w z + c - u). gate !done (+reject if redo)
-void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, double* u, double* y, int nf, int mode,
-                    int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var = GroupVar());
+// Z variant: u = uin + w(Px - z) [mode 0] or u = grad E(z)/w [mode 1]; then y = w(w z + c - u) (mode 2: of uin,
+// nothing written to u). uin may be u. gate !done (+reject if redo)
+void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, const double* uin, double* u, double* y,
+                    int nf, int mode, int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var = GroupVar());
 // prim2 partials of |w(Px - z)|^2 and optionally dual2 partials of |w(z - zref)|^2. gate !done (+reject if redo)
 void launch_prim_z(const GroupDev& g, const double* xfull, const double* z, const double* zref, int nf, int redo,
                    Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s);
@@ -124,6 +125,7 @@ void launch_rhs(int nf, const int* ptr, const int* row, const double* val, const
                 int nb_final = 0);
 // UX reject test + restore fused (replaces CTL_PRIM_CHECK + launch_restore_ux)
 // Z variant: k_control's CTL_PRIM_CHECK_Z and the reject branch's three restores in one launch
+// (u null: x and z only)
 void launch_check_restore_z(Ctrl* ctrl, const double* red, int nb, int accel, double* u, double* x, double* z,
                             const double* du, const double* dx, const double* dz, long long nz, long long nx,
                             hipStream_t s);
