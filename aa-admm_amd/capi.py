@@ -24,7 +24,7 @@ EXPORTS = [
     "aa_ctx_warm_dense", "aa_lame_from_young",
     "aa_settings_default", "aa_elastic_create", "aa_elastic_destroy", "aa_elastic_add_nodes", "aa_elastic_add_tets",
     "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
-    "aa_elastic_add_obstacle", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
+    "aa_elastic_add_obstacle", "aa_elastic_add_mesh_obstacle", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
     "aa_elastic_num_nodes", "aa_elastic_get_x", "aa_elastic_get_v", "aa_elastic_set_v", "aa_elastic_get_history",
     "aa_elastic_get_times", "aa_elastic_set_iterations", "aa_elastic_set_x",
     "aa_elastic_runtime", "aa_elastic_bench_iterations", "aa_elastic_kernel_stats", "aa_elastic_local_stats",
@@ -34,7 +34,7 @@ EXPORTS = [
     "aa_geom_create", "aa_geom_create_kind", "aa_geom_destroy", "aa_geom_add_ref_surface", "aa_geom_add_constraints", "aa_geom_add_laplacian",
     "aa_geom_add_closeness", "aa_geom_add_laplacians", "aa_geom_add_closenesses", "aa_geom_setup", "aa_geom_solve", "aa_geom_set_stop", "aa_geom_get_solution", "aa_geom_get_history",
     "aa_geom_runtime_info", "aa_geom_closest_points", "aa_geom_bench_iterations", "aa_geom_kernel_stats",
-    "aa_test_prox", "aa_test_cod_solve", "aa_test_geom_project",
+    "aa_test_prox", "aa_test_cod_solve", "aa_test_geom_project", "aa_test_mesh_sdf", "aa_test_collision_prox",
 ]
 
 # Geometry constraint types (Geometry/Constraint.h) and SPD solver types (SolverCommon.h)
@@ -345,6 +345,16 @@ class Solver:
         p[:len(q)] = q
         _chk(lib().aa_elastic_add_obstacle(self.h, C.c_int(kind), _dp(p)))
 
+    def add_mesh_obstacle(self, V, F):
+        """PassiveMesh as a closed, outward-oriented triangle surface: vertices V (n, 3), triangles
+        F (m, 3). Takes its place in add_obstacle's insertion order; returns the mesh's number."""
+        v = np.ascontiguousarray(V, np.float64).reshape(-1)
+        f = np.ascontiguousarray(F, np.int32).reshape(-1)
+        k = C.c_int()
+        _chk(lib().aa_elastic_add_mesh_obstacle(self.h, _dp(v), C.c_int(len(v) // 3), _ip(f), C.c_int(len(f) // 3),
+                                                C.byref(k)))
+        return k.value
+
     def set_collisions(self, inds):
         i = np.ascontiguousarray(inds, np.int32).reshape(-1)
         _chk(lib().aa_elastic_set_collisions(self.h, _ip(i), C.c_int(len(i))))
@@ -483,6 +493,8 @@ def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
     s.set_pins(scene.pin_idx, scene.pin_pts)
     for kind, prm in getattr(scene, "obstacles", []):
         s.add_obstacle(kind, prm)
+    for V, F in getattr(scene, "mesh_obstacles", []):   # after the analytic ones in the insertion order
+        s.add_mesh_obstacle(V, F)
     if getattr(scene, "collision_idx", None) is not None:
         s.set_collisions(scene.collision_idx)
     for tris, direction in getattr(scene, "winds", []):
@@ -756,3 +768,36 @@ def hook_geom_project(ctx: Context, ctype, k, params, P):
     _chk(lib().aa_test_geom_project(ctx.h, C.c_int(ctype), C.c_int(k), _dp(prm), _dp(P), C.c_int(P.shape[0]), _dp(out)))
     return out
 
+
+def hook_mesh_sdf(ctx: Context, V, F, Q):
+    """The mesh obstacle's signed distance on queries Q (n, 3): (closest points, dx, triangle) with
+    dx = -|q - c| inside and +|q - c| otherwise, the triangle in F's numbering."""
+    v = np.ascontiguousarray(V, np.float64).reshape(-1)
+    f = np.ascontiguousarray(F, np.int32).reshape(-1)
+    q = np.ascontiguousarray(Q, np.float64).reshape(-1, 3)
+    n = q.shape[0]
+    c, dx, tri = np.zeros((n, 3)), np.zeros(n), np.zeros(n, np.int32)
+    _chk(lib().aa_test_mesh_sdf(ctx.h, _dp(v), C.c_int(len(v) // 3), _ip(f), C.c_int(len(f) // 3), _dp(q), C.c_int(n),
+                                _dp(c), _dp(dx), _ip(tri)))
+    return c, dx, tri
+
+
+def hook_collision_prox(ctx: Context, obstacles, meshes, Q):
+    """Collision::prox of candidates Q (n, 3) against `obstacles` in insertion order: (type, params)
+    pairs, a mesh as (AA_OBS_MESH, [m]) naming meshes[m] = (V, F)."""
+    rows = np.zeros((len(obstacles), 8))
+    for k, (kind, prm) in enumerate(obstacles):
+        a = np.asarray(prm, np.float64).reshape(-1)
+        rows[k, 0] = kind
+        rows[k, 1:1 + len(a)] = a
+    vs = [np.ascontiguousarray(V, np.float64).reshape(-1, 3) for V, _ in meshes]
+    fs = [np.ascontiguousarray(F, np.int32).reshape(-1, 3) for _, F in meshes]
+    vptr = np.concatenate([[0], np.cumsum([len(v) for v in vs])]).astype(np.int32)
+    fptr = np.concatenate([[0], np.cumsum([len(f) for f in fs])]).astype(np.int32)
+    vv = np.ascontiguousarray(np.concatenate(vs) if vs else np.zeros((1, 3)))
+    ff = np.ascontiguousarray(np.concatenate(fs) if fs else np.zeros((1, 3), np.int32))
+    q = np.ascontiguousarray(Q, np.float64).reshape(-1, 3)
+    out = np.zeros_like(q)
+    _chk(lib().aa_test_collision_prox(ctx.h, _dp(rows), C.c_int(len(obstacles)), _dp(vv), _ip(vptr), _ip(ff), _ip(fptr),
+                                      C.c_int(len(meshes)), _dp(q), C.c_int(q.shape[0]), _dp(out)))
+    return out

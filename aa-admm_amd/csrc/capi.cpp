@@ -5,6 +5,7 @@
 #include <exception>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/aa_admm.h"
 #include "comm.hpp"
@@ -16,6 +17,8 @@ struct aa_ctx_s { aa::Context c; };
 struct aa_elastic_s { aa::ElasticSolver* s; aa_ctx_s* ctx; };
 struct aa_geom_s { aa::GeomSolver* s; aa_ctx_s* ctx; };
 struct aa_comm_s { std::unique_ptr<aa::Comm> c; };
+
+static_assert(AA_MAX_MESH_OBSTACLES == aa::kMaxMeshObstacles && AA_OBS_MESH == aa::OBS_MESH, "aa_admm.h and the library agree");
 
 namespace {
 thread_local std::string g_err;
@@ -185,6 +188,15 @@ int aa_elastic_add_obstacle(aa_elastic h, int type, const double* params) {
         NEED(h, "null handle");
         AA_HIP(hipSetDevice(h->ctx->c.device));
         h->s->add_obstacle(type, params);
+    });
+}
+
+int aa_elastic_add_mesh_obstacle(aa_elastic h, const double* verts3, int n_verts, const int* tris3, int n_tris, int* id) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
+        const int k = h->s->add_mesh_obstacle(verts3, n_verts, tris3, n_tris);
+        if (id) *id = k;
     });
 }
 
@@ -533,6 +545,63 @@ extern "C" int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double
         aa::launch_test_prox(op, prm4, di.p, n, dout.p, dit.p, s);
         AA_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * D * n, hipMemcpyDeviceToHost, s));
         if (iters) AA_HIP(hipMemcpyAsync(iters, dit.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+        AA_HIP(hipStreamSynchronize(s));
+    });
+}
+
+extern "C" int aa_test_mesh_sdf(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
+                               const double* q3, int n, double* closest3, double* dx, int* tri) {
+    return with_device_arrays(ctx, [&](hipStream_t s) {
+        NEED(q3 && closest3 && dx && tri && n >= 0, "aa_test_mesh_sdf: bad argument");
+        const aa::MeshObstacleHost M = aa::prepare_mesh_obstacle(verts3, n_verts, tris3, n_tris);
+        aa::MeshObsBuffers buf;
+        const aa::MeshObsDev d = buf.upload(M, s);
+        aa::DevBuf<aa::MeshObsDev> dd;
+        dd.upload(&d, 1, s);
+        aa::DevBuf<double> dq, dc((size_t)3 * std::max(n, 1)), ddx(std::max(n, 1));
+        aa::DevBuf<int> dt(std::max(n, 1));
+        dq.upload(q3, (size_t)3 * n, s);
+        aa::launch_test_mesh_sdf(dd.p, dq.p, n, dc.p, ddx.p, dt.p, s);
+        AA_HIP(hipMemcpyAsync(closest3, dc.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(dx, ddx.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(tri, dt.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+        AA_HIP(hipStreamSynchronize(s));
+    });
+}
+
+extern "C" int aa_test_collision_prox(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
+                                     const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr,
+                                     int n_meshes, const double* q3, int n, double* out3) {
+    return with_device_arrays(ctx, [&](hipStream_t s) {
+        NEED(q3 && out3 && n >= 0 && n_obs >= 0 && n_obs <= aa::kMaxObstacles && (obs_rows || n_obs == 0),
+             "aa_test_collision_prox: bad argument");
+        NEED(n_meshes >= 0 && n_meshes <= aa::kMaxMeshObstacles, "aa_test_collision_prox: too many mesh obstacles");
+        NEED(n_meshes == 0 || (mesh_verts3 && mesh_vert_ptr && mesh_tris3 && mesh_tri_ptr), "aa_test_collision_prox: null mesh arrays");
+        std::vector<std::unique_ptr<aa::MeshObsBuffers>> bufs;
+        std::vector<aa::MeshObsDev> table((size_t)std::max(n_meshes, 1));
+        for (int m = 0; m < n_meshes; ++m) {
+            const aa::MeshObstacleHost M = aa::prepare_mesh_obstacle(
+                mesh_verts3 + 3 * (size_t)mesh_vert_ptr[m], mesh_vert_ptr[m + 1] - mesh_vert_ptr[m],
+                mesh_tris3 + 3 * (size_t)mesh_tri_ptr[m], mesh_tri_ptr[m + 1] - mesh_tri_ptr[m]);
+            bufs.push_back(std::make_unique<aa::MeshObsBuffers>());
+            table[m] = bufs.back()->upload(M, s);
+        }
+        std::vector<double> h(1 + (size_t)aa::kObsStride * n_obs, 0.0);
+        h[0] = n_obs;
+        for (int k = 0; k < n_obs; ++k) {
+            const double* o = obs_rows + (size_t)aa::kObsStride * k;
+            const int type = (int)o[0];
+            NEED(type >= aa::OBS_FLOOR && type <= aa::OBS_MESH, "aa_test_collision_prox: unknown obstacle type");
+            NEED(type != aa::OBS_MESH || (o[1] >= 0 && o[1] < n_meshes && o[1] == (int)o[1]), "aa_test_collision_prox: mesh id out of range");
+            std::copy(o, o + aa::kObsStride, h.begin() + 1 + (size_t)aa::kObsStride * k);
+        }
+        aa::DevBuf<aa::MeshObsDev> dtab;
+        dtab.upload(table, s);
+        aa::DevBuf<double> dobs, dq, dout((size_t)3 * std::max(n, 1));
+        dobs.upload(h, s);
+        dq.upload(q3, (size_t)3 * n, s);
+        aa::launch_test_collision_prox(dobs.p, dtab.p, dq.p, n, dout.p, s);
+        AA_HIP(hipMemcpyAsync(out3, dout.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
         AA_HIP(hipStreamSynchronize(s));
     });
 }

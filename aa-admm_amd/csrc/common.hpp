@@ -8,14 +8,9 @@
 #include <string>
 #include <vector>
 
+#include "error.hpp"
+
 namespace aa {
-
-enum Status { OK = 0, ERR_ARG = -1, ERR_STATE = -2, ERR_DEVICE = -3, ERR_NUMERIC = -4 };
-
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 #define AA_HIP(call)                                                                                   \
     do {                                                                                               \

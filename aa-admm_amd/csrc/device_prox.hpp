@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "bvh_device.hpp"
 #include "elastic_kernels.hpp"
 
 namespace aa {
@@ -228,6 +229,37 @@ __device__ __forceinline__ void tet_linear_grad(const double* z, double kvol, do
         }
 }
 
+// Signed distance of q to a mesh obstacle (mesh_obstacle.hpp). Returns whether q is inside; then
+// dx = -|q - c|, c = the closest surface point and tri its triangle (leaf order). c and tri are
+// exactly bvh_closest's, cold start; the feature c lies on is read from closest_on_tri's branch on
+// that triangle (the same arithmetic on the same inputs, so the same c), and q is inside iff
+// (q - c) . n < 0 for the feature's pseudonormal n.
+// A point outside the root box is not inside and skips the walk. Those lanes are masked off for
+// the whole of bvh_closest: its two-phase schedule counts lanes with __ballot, which reads 0 for
+// an inactive lane in both `live` and `held`, so a culled lane is neither waited for nor counted
+// toward the hold share -- the schedule sees a wave of the remaining lanes only.
+__device__ inline double mesh_closest_signed(const MeshObsDev& mo, const double* q, double* c, int& tri) {
+#pragma clang fp contract(off)
+    double cx, cy, cz;
+    tri = bvh_closest(mo.surf, q[0], q[1], q[2], -1, cx, cy, cz);
+    int region = TRI_FACE;
+    closest_on_tri(mo.surf.tris[tri].v, q[0], q[1], q[2], cx, cy, cz, region);
+    c[0] = cx; c[1] = cy; c[2] = cz;
+    const double* n = mo.pn + (size_t)kPnStride * tri + 3 * region;
+    return (q[0] - cx) * n[0] + (q[1] - cy) * n[1] + (q[2] - cz) * n[2];
+}
+__device__ inline bool mesh_in_root_box(const MeshObsDev& mo, const double* q) {
+    return q[0] >= mo.lo[0] && q[0] <= mo.hi[0] && q[1] >= mo.lo[1] && q[1] <= mo.hi[1] && q[2] >= mo.lo[2] &&
+           q[2] <= mo.hi[2];
+}
+__device__ inline bool mesh_signed_distance(const MeshObsDev& mo, const double* q, double& dx, double* c, int& tri) {
+    if (!mesh_in_root_box(mo, q)) return false;
+    if (!(mesh_closest_signed(mo, q, c, tri) < 0.0)) return false;
+    dx = -sqrt(dist2(q[0], q[1], q[2], c[0], c[1], c[2]));
+    return true;
+}
+__device__ __forceinline__ const MeshObsDev* mesh_table_of(const MeshObsDev* t) { return t; }
+
 // (1/w) * ((w x + u) - c) of an identity-reduction row, without FMA contraction (c = -w x_pin for
 // a pinned node, whose x enters through c: the same sum)
 __device__ inline void collision_candidate(const double* x, const double* u, double w, double* q) {
@@ -243,7 +275,13 @@ __device__ inline void collision_candidate(const double* x, const double* u, dou
 // signed-distance functions restate PassiveObject.hpp:32-136 with the reference's operation
 // order (no FMA contraction, Eigen's norm / normalize: division by sqrt of the squared norm).
 // Obstacle table: obs[0] = count, then kObsStride doubles each: type, parameters.
-__device__ inline void collision_prox(const double* q, const double* obs, double* out) {
+// Mesh-aware form: a trailing mesh table (the collision group's parameter pack, as GroupVar is
+// the per-element materials') adds the OBS_MESH rows, o[1] = the mesh's row in the table. An
+// inside hit replaces the running (dx, point) unconditionally -- PassiveMesh::signed_distance has
+// no `if (dx > p.dx) return;` (PassiveObject.hpp:160-175) -- and a miss leaves it untouched.
+// Without the table the code is the analytic shapes' alone.
+template <class... M>
+__device__ inline void collision_prox(const double* q, const double* obs, double* out, M... meshes) {
 #pragma clang fp contract(off)
     double best = 1.79769313486231570815e+308;   // std::numeric_limits<double>::max()
     double pt[3] = {0.0, 0.0, 0.0};
@@ -281,6 +319,16 @@ __device__ inline void collision_prox(const double* q, const double* obs, double
                 if (z2 > 0.0) { d0 /= nrm; d1 /= nrm; d2 /= nrm; }
                 p0 = o[1] + d0 * o[4]; p1 = o[2] + d1 * o[4]; p2 = o[3] + d2 * o[4];
             }
+        } else if (sizeof...(M) != 0 && type == OBS_MESH) {   // PassiveMesh            :138-178
+            if constexpr (sizeof...(M) != 0) {
+                const MeshObsDev& mo = mesh_table_of(meshes...)[(int)o[1]];
+                double c[3];
+                int tri;
+                if (!mesh_signed_distance(mo, q, dx, c, tri)) continue;
+                best = dx;
+                pt[0] = c[0]; pt[1] = c[1]; pt[2] = c[2];
+            }
+            continue;
         } else {                                      // Cylinder(center, rad), axis z :118-136
             double d0 = q[0] - o[1], d1 = q[1] - o[2], d2 = 0.0 - o[3];
             const double z2 = sq3(d0, d1, d2), nrm = sqrt(z2);

@@ -175,6 +175,33 @@ void ElasticSolver::add_obstacle(int type, const double* prm) {
     if (initialized_) upload_obstacles();
 }
 
+// PassiveMesh: validated and prepared on the host (mesh_obstacle.hpp), uploaded here, and entered
+// in the obstacle list as a row {OBS_MESH, table row}. The first mesh switches the collision
+// group to its mesh-aware kernel, so a graph captured with the plain one is dropped and captured
+// again at the next step; later meshes only fill another row of the table.
+int ElasticSolver::add_mesh_obstacle(const double* V3, int nv, const int* F3, int nf) {
+    if ((int)obstacles_.size() >= kMaxObstacles) throw Error(ERR_ARG, "add_mesh_obstacle: too many obstacles");
+    if ((int)meshes_.size() >= kMaxMeshObstacles)
+        throw Error(ERR_ARG, "add_mesh_obstacle: too many mesh obstacles (at most " + std::to_string(kMaxMeshObstacles) + ")");
+    const MeshObstacleHost M = prepare_mesh_obstacle(V3, nv, F3, nf);
+    auto mo = std::make_unique<MeshObsBuffers>();
+    const MeshObsDev d = mo->upload(M, s());
+    if (!mesh_dev_.p) mesh_dev_.alloc(kMaxMeshObstacles);
+    const int row = (int)meshes_.size();
+    AA_HIP(hipMemcpyAsync(mesh_dev_.p + row, &d, sizeof(d), hipMemcpyHostToDevice, s()));
+    AA_HIP(hipStreamSynchronize(s()));
+    meshes_.push_back(std::move(mo));
+    std::array<double, kObsStride> o{};
+    o[0] = OBS_MESH;
+    o[1] = row;
+    obstacles_.push_back(o);
+    if (initialized_) {
+        if (row == 0) drop_graph();
+        upload_obstacles();
+    }
+    return row;
+}
+
 void ElasticSolver::upload_obstacles() {
     if (!obs_dev_.p) return;
     std::vector<double> h(1 + kObsStride * obstacles_.size());
@@ -795,7 +822,7 @@ void ElasticSolver::local_z_all(const double* xfull, const double* u, double* z,
     if (timed) ev_begin("local_z");
     for (auto& g : groups_) {
         launch_local_z(g.d, xfull, u, z, y, nf_, st_.variant, mode, ctrl_.p, red ? pa_ : nullptr, off, s(),
-                       use_queue_ ? &lq_ : nullptr, g.var);
+                       use_queue_ ? &lq_ : nullptr, g.var, mesh_table(g.d));
         off += blocks_for(g.d.count);
     }
     if (timed) ev_end("local_z");
@@ -806,7 +833,7 @@ void ElasticSolver::local_z_on(const double* xfull, const double* u, double* z, 
                                const LocalQueue* q) {
     for (auto& g : groups_)
         launch_local_z(g.d, xfull, u, z, nullptr, nf_, st_.variant, mode, c, nullptr, 0, st, use_queue_ ? q : nullptr,
-                       g.var);
+                       g.var, mesh_table(g.d));
 }
 
 void ElasticSolver::prologue() {

@@ -12,12 +12,33 @@
 #include "common.hpp"
 #include "direct_solve.hpp"
 #include "elastic_kernels.hpp"
+#include "mesh_obstacle.hpp"
 
 namespace aa {
 
 struct Context {
     int device = 0;
     hipStream_t stream = nullptr;
+};
+
+// Device storage of one prepared mesh obstacle; upload returns the view the kernels read
+struct MeshObsBuffers {
+    DevBuf<BvhNode> nodes;
+    DevBuf<BvhTri> tris;
+    DevBuf<double> pn;
+    DevBuf<int> orig;
+    MeshObsDev upload(const MeshObstacleHost& M, hipStream_t s) {
+        nodes.upload(M.nodes, s);
+        tris.upload(M.tris, s);
+        pn.upload(M.pn, s);
+        orig.upload(M.orig, s);
+        MeshObsDev d{};
+        d.surf.nodes = nodes.p; d.surf.tris = tris.p;
+        d.surf.n_nodes = (int)M.nodes.size(); d.surf.n_tris = (int)M.tris.size();
+        d.pn = pn.p; d.orig = orig.p;
+        for (int k = 0; k < 3; ++k) { d.lo[k] = M.lo[k]; d.hi[k] = M.hi[k]; }
+        return d;
+    }
 };
 
 class ElasticSolver {
@@ -33,6 +54,9 @@ public:
     // energy-based collisions of the (u,x) variant (admm_anderson_hard_zxu Solver.cpp:318-348)
     void add_obstacle(int type, const double* params);
     void set_collisions(const int* inds, int n);
+    // PassiveMesh (PassiveObject.hpp:138-178) as a closed triangle surface (mesh_obstacle.hpp);
+    // takes its place in add_obstacle's insertion order. Returns the mesh's row in the table.
+    int add_mesh_obstacle(const double* verts3, int n_verts, const int* tris3, int n_tris);
     // WindForce (ExplicitForce.hpp:39-47) on the given triangles; returns its id
     int add_wind(const int* tris3, int ntris, const double* dir3);
     void set_wind(int id, const double* dir3);
@@ -98,6 +122,12 @@ private:
     std::vector<std::unique_ptr<Wind>> winds_;
     DevBuf<double> obs_dev_;
     void upload_obstacles();
+    // mesh obstacles: each one's BVH and pseudonormals, and the table of their device views the
+    // mesh-aware collision prox indexes (kMaxMeshObstacles rows, allocated once: a fixed address,
+    // so a captured graph stays valid when a later mesh fills another row)
+    std::vector<std::unique_ptr<MeshObsBuffers>> meshes_;
+    DevBuf<MeshObsDev> mesh_dev_;
+    const MeshObsDev* mesh_table(const GroupDev& d) const { return d.kind == 2 && !meshes_.empty() ? mesh_dev_.p : nullptr; }
     void build_wind(Wind& w);
     std::vector<int> pin_order_;
     aa_settings st_{};

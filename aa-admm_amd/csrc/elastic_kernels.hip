@@ -242,7 +242,8 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
             // row (EnergyTerm.hpp:166-178: z = W^-1 (W x + u - c), W^-1 stored as 1/w): the
             // contact decision is discrete, so the candidate is rounded like the reference's
             if (variant == 1) dev::collision_candidate(F, uu, w, vin);
-            dev::collision_prox(vin, g.obs, zz);
+            if constexpr (VAR) dev::collision_prox(vin, g.obs, zz, gvp...);   // the pack is the mesh table
+            else dev::collision_prox(vin, g.obs, zz);
         } else if constexpr (NV == 3) {
             if constexpr (VAR) dev::tri_prox(vin, zz, variant, var_of(gvp...).lmin[e], var_of(gvp...).lmax[e]);
             else dev::tri_prox(vin, zz, variant, g.lmin, g.lmax);
@@ -1701,6 +1702,38 @@ __global__ void k_test_prox(int op, double E, double nu, double p2, double p3, c
     if (iters) iters[e] = it;
 }
 
+// aa_test_mesh_sdf: the production mesh_signed_distance decides `inside` (root-box cull included);
+// a query it turns away is walked all the same for the report (c, +|q - c|, triangle)
+__global__ __launch_bounds__(kBlock) void k_test_mesh_sdf(const MeshObsDev* __restrict__ mesh, const double* __restrict__ q,
+                                                          int n, double* __restrict__ closest, double* __restrict__ dx,
+                                                          int* __restrict__ tri) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const MeshObsDev& mo = *mesh;
+    const double p[3] = {q[3 * (size_t)e], q[3 * (size_t)e + 1], q[3 * (size_t)e + 2]};
+    double c[3], d = 0.0;
+    int t = -1;
+    if (!dev::mesh_signed_distance(mo, p, d, c, t)) {
+        dev::mesh_closest_signed(mo, p, c, t);
+        d = sqrt(dist2(p[0], p[1], p[2], c[0], c[1], c[2]));
+    }
+    for (int i = 0; i < 3; ++i) closest[3 * (size_t)e + i] = c[i];
+    dx[e] = d;
+    tri[e] = mo.orig[t];
+}
+
+__global__ __launch_bounds__(kBlock) void k_test_collision_prox(const double* __restrict__ obs,
+                                                                const MeshObsDev* __restrict__ meshes,
+                                                                const double* __restrict__ q, int n,
+                                                                double* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const double p[3] = {q[3 * (size_t)e], q[3 * (size_t)e + 1], q[3 * (size_t)e + 2]};
+    double z[3];
+    dev::collision_prox(p, obs, z, meshes);
+    for (int i = 0; i < 3; ++i) out[3 * (size_t)e + i] = z[i];
+}
+
 __global__ __launch_bounds__(kSolveBlock) void k_test_cod(int n, const double* __restrict__ M, const double* __restrict__ b,
                                                           double* __restrict__ x) {
     __shared__ CodLds S;
@@ -1741,7 +1774,7 @@ LocalQueue make_local_queue(int device, int* counter) {
 
 void launch_local_z(const GroupDev& g, const double* xfull, const double* u, double* z, double* y, int nf,
                     int variant, int mode, Ctrl* ctrl, double* red, int red_off, hipStream_t s, const LocalQueue* queue,
-                    const GroupVar& var) {
+                    const GroupVar& var, const MeshObsDev* meshes) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
     if (g.kind == 0 && g.mat != 0 && !red && queue && queue->counter) {   // hyperelastic, no partials: work queue
@@ -1778,7 +1811,8 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
         AA_CHECK_LAUNCH();
         return;
     }
-    if (g.kind == 2) hipLaunchKernelGGL((k_local_z<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+    if (g.kind == 2 && meshes) hipLaunchKernelGGL((k_local_z<1, 0, const MeshObsDev*>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, meshes);
+    else if (g.kind == 2) hipLaunchKernelGGL((k_local_z<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
     else if (g.kind == 1 && var) hipLaunchKernelGGL((k_local_z<3, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, var);
     else if (g.kind == 1) hipLaunchKernelGGL((k_local_z<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
     else if (g.mat == 0) hipLaunchKernelGGL((k_local_z<4, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);   // the linear prox reads w only
@@ -2053,6 +2087,20 @@ void launch_test_prox(int op, const double* prm4, const double* in, int n, doubl
 
 void launch_test_cod(int n, const double* M, const double* b, double* x, hipStream_t s) {
     hipLaunchKernelGGL(k_test_cod, dim3(1), dim3(kSolveBlock), 0, s, n, M, b, x);
+    AA_CHECK_LAUNCH();
+}
+
+void launch_test_mesh_sdf(const MeshObsDev* mesh, const double* q, int n, double* closest, double* dx, int* tri,
+                          hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_test_mesh_sdf, dim3(blocks_for(n)), dim3(kBlock), 0, s, mesh, q, n, closest, dx, tri);
+    AA_CHECK_LAUNCH();
+}
+
+void launch_test_collision_prox(const double* obs, const MeshObsDev* meshes, const double* q, int n, double* out,
+                                hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_test_collision_prox, dim3(blocks_for(n)), dim3(kBlock), 0, s, obs, meshes, q, n, out);
     AA_CHECK_LAUNCH();
 }
 

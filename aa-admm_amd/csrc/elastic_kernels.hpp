@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "bvh.hpp"
+
 namespace aa {
 
 constexpr int kMaxM = 32;          // largest Anderson window supported on device
@@ -39,7 +41,8 @@ struct GroupVar {
     explicit operator bool() const { return k != nullptr; }
 };
 // passive obstacles of the collision terms (PassiveObject.hpp:32-136): type, then up to 7 parameters
-enum ObsType { OBS_FLOOR = 0, OBS_SLIDE_FLOOR = 1, OBS_SPHERE = 2, OBS_PLANE_HALF_SPHERE = 3, OBS_CYLINDER = 4 };
+// OBS_MESH (PassiveMesh, :138-178): a triangle-mesh obstacle, parameter 1 = its row in the mesh table
+enum ObsType { OBS_FLOOR = 0, OBS_SLIDE_FLOOR = 1, OBS_SPHERE = 2, OBS_PLANE_HALF_SPHERE = 3, OBS_CYLINDER = 4, OBS_MESH = 5 };
 constexpr int kObsStride = 8, kMaxObstacles = 256;
 __host__ __device__ constexpr int ncol_of(int nv) { return nv > 1 ? nv - 1 : 1; }   // 1 vertex: identity reduction
 
@@ -104,9 +107,12 @@ LocalQueue make_local_queue(int device, int* counter);
 // z = prox(P x + u/w); prim partials; optional y = w(w z + c - u). gate: !done (and reject for REDO)
 // queue given: hyperelastic groups without partials run as a persistent work queue
 // var given (launch_u_and_y too): the group's per-element material instantiation of the same kernel
+// meshes given: the collision group's mesh-aware instantiation (obstacle rows of type OBS_MESH
+// index this table); null: the analytic shapes' instantiation
 void launch_local_z(const GroupDev& g, const double* xfull, const double* u, double* z, double* y, int nf,
                     int variant, int mode, Ctrl* ctrl, double* red, int red_off, hipStream_t s,
-                    const LocalQueue* queue = nullptr, const GroupVar& var = GroupVar());
+                    const LocalQueue* queue = nullptr, const GroupVar& var = GroupVar(),
+                    const MeshObsDev* meshes = nullptr);
 // r = w(P x - z); prim2/dual2 partials; u += r (UX variant update_u fused with the residual)
 void launch_resid_update_u(const GroupDev& g, const double* xfull, const double* xlast, const double* z, double* u,
                            int nf, Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s);
@@ -183,5 +189,11 @@ void launch_aa_mix(Seg2 G, double* cur, long long eff, double* dF, double* dG, C
 // ---- element-level test hooks (aa_test_* in the C ABI; tests only)
 void launch_test_prox(int op, const double* prm4, const double* in, int n, double* out, int* iters, hipStream_t s);
 void launch_test_cod(int n, const double* M, const double* b, double* x, hipStream_t s);
+// aa_test_mesh_sdf: per query the closest point, dx (-|q - c| inside, +|q - c| otherwise) and the
+// triangle in the caller's numbering; aa_test_collision_prox: collision_prox on n candidates
+void launch_test_mesh_sdf(const MeshObsDev* mesh, const double* q, int n, double* closest, double* dx, int* tri,
+                          hipStream_t s);
+void launch_test_collision_prox(const double* obs, const MeshObsDev* meshes, const double* q, int n, double* out,
+                                hipStream_t s);
 
 }  // namespace aa

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "bvh.hpp"               // BvhNode, BvhTri, SurfDev
 #include "elastic_kernels.hpp"   // Ctrl, Seg2, Anderson launchers
 
 namespace aa {
@@ -10,47 +11,6 @@ namespace aa {
 // constraint types (Geometry/Constraint.h) -- must match include/aa_admm.h AA_CON_*
 enum GeoType { GEO_PLANE = 0, GEO_ANGLE = 1, GEO_EDGE = 2, GEO_CLOSENESS = 3, GEO_POINT_TO_REF = 4, GEO_REF_SURFACE = 5 };
 constexpr int kGeoMaxK = 8;   // planes up to this valence run in registers; larger ones in slot-row scratch
-
-// Bounding-volume hierarchy over one reference triangle surface (closest-point queries of
-// PointToRefSurfaceConstraint / ReferenceSurfceConstraint). Nodes in depth-first order:
-// the left child of node i is i+1; `a` is the right child (inner) or the first triangle
-// (leaf), `b` = -(triangle count) for a leaf, 0 otherwise; `skip` is the first node after
-// this node's subtree (the escape link of a stackless traversal).
-// 64-B BVH node: box in fp32 rounded OUTWARD (never prunes a box the fp64 box would keep),
-// a = right child (inner) or first triangle (leaf), sn = escape link (node after the subtree,
-// low 29 bits) | leaf triangle count << 29 (0 = inner), and a slab: the subtree's mean unit
-// normal n and the range [dlo, dhi] of n . v over its vertices (rounded outward). The slab
-// bounds the distance to every triangle of the subtree from below like the box does, and is
-// far tighter for sloped, thin patches seen from afar (a point well off the surface).
-// With the two tangent axes t1, t2 (principal directions of the subtree's vertices in the plane
-// normal to n) and their ranges the slab becomes an oriented box: a point far above a flat
-// patch has the same normal distance to every patch around its foot point, and only the
-// tangent ranges tell those patches apart. 128 B, one cache line.
-struct alignas(128) BvhNode {
-    float lo[3], hi[3];
-    int a;
-    unsigned sn;
-    float nrm[3], dlo, dhi;
-    float t1[3], t1lo, t1hi;
-    float t2[3], t2lo, t2hi;
-};
-static_assert(sizeof(BvhNode) == 128, "BvhNode is one 128-B line");
-__host__ __device__ inline int bvh_skip(const BvhNode& n) { return (int)(n.sn & 0x1fffffffu); }
-__host__ __device__ inline int bvh_count(const BvhNode& n) { return (int)(n.sn >> 29); }
-struct BvhTri { double v[9]; };   // triangle corners, stored in leaf order
-// The same tree collapsed to `wide_g` (4 or 8) children per node for the group traversal
-// (wide_g lanes per query, see bvh_closest_grp): node w's children are the records
-// wide[w * wide_g + k], copies of the BvhNode of a descendant log2(wide_g) levels down (or of a
-// leaf met earlier), with `a` = the child's wide node (inner) or its first triangle (leaf) and
-// sn = triangle count << 29 (0 = inner); unused slots have a = -1. wide_g = 0: not built.
-constexpr int kCpStack = 64;   // per-query traversal stack entries of the group traversal
-struct SurfDev {
-    const BvhNode* nodes;
-    const BvhTri* tris;
-    int n_nodes, n_tris;
-    const BvhNode* wide = nullptr;
-    int wide_g = 0;
-};
 
 // One homogeneous block of constraints (same type / index count / weight / hard-soft).
 struct GeoGroupDev {

@@ -1,0 +1,160 @@
+// Host preparation of a triangle-mesh passive obstacle of the collision terms (the reference's
+// PassiveMesh, admm_anderson_hard_zxu/src/PassiveObject.hpp:138-178: a collision node inside the
+// mesh moves to the nearest surface point). Host only, no HIP.
+//
+// The obstacle is a closed, edge-manifold, outward-oriented triangle surface. A query q is
+// answered in fp64 by the project's exact closest-point walk (bvh_device.hpp bvh_closest) and
+// signed by the angle-weighted pseudonormal n of the feature the closest point c lies on
+// (Baerentzen & Aanaes, "Signed distance computation using the angle weighted pseudonormal",
+// IEEE TVCG 11(3), 2005): inside iff (q - c) . n < 0. The sign is right for every q only on a
+// closed manifold surface, hence the validation; n need not be of unit length.
+//   face   -- the unit face normal;
+//   edge   -- the sum of the two incident unit face normals;
+//   vertex -- the sum over incident faces of (incident angle x unit face normal).
+#pragma once
+#include <algorithm>
+#include <array>
+#include <cfloat>
+#include <cmath>
+#include <map>
+#include <numeric>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "bvh.hpp"
+#include "bvh_build.hpp"
+#include "error.hpp"
+
+namespace aa {
+
+constexpr int kMaxMeshObstacles = 16;   // rows of a solver's mesh table (aa_admm.h)
+
+struct MeshObstacleHost {
+    std::vector<BvhNode> nodes;
+    std::vector<BvhTri> tris;     // leaf order
+    std::vector<double> pn;       // [tris][kPnStride], leaf order; feature k at 3 k (TriRegion order:
+                                  // corner a, corner b, edge ab, corner c, edge ca, edge bc, face)
+    std::vector<int> orig;        // leaf order -> the caller's triangle index
+    double lo[3], hi[3];          // exact range of the surface's vertices
+};
+
+namespace mesh_detail {
+inline void sub3(const double* a, const double* b, double* r) { r[0] = a[0] - b[0]; r[1] = a[1] - b[1]; r[2] = a[2] - b[2]; }
+inline void cross3(const double* u, const double* w, double* r) {
+    r[0] = u[1] * w[2] - u[2] * w[1]; r[1] = u[2] * w[0] - u[0] * w[2]; r[2] = u[0] * w[1] - u[1] * w[0];
+}
+inline double dot3(const double* u, const double* w) { return u[0] * w[0] + u[1] * w[1] + u[2] * w[2]; }
+}  // namespace mesh_detail
+
+// Throws Error(ERR_ARG) naming the first offending vertex, triangle or edge.
+inline void validate_mesh_obstacle(const double* V, int nv, const int* F, int nf) {
+    using namespace mesh_detail;
+    const std::string who = "add_mesh_obstacle: ";
+    if (!V || !F || nv <= 0 || nf <= 0) throw Error(ERR_ARG, who + "empty mesh");
+    for (int t = 0; t < nf; ++t)
+        for (int a = 0; a < 3; ++a)
+            if (F[3 * (size_t)t + a] < 0 || F[3 * (size_t)t + a] >= nv)
+                throw Error(ERR_ARG, who + "triangle " + std::to_string(t) + " has a vertex index out of range");
+    for (int i = 0; i < nv; ++i)
+        for (int d = 0; d < 3; ++d)
+            if (!std::isfinite(V[3 * (size_t)i + d]))
+                throw Error(ERR_ARG, who + "vertex " + std::to_string(i) + " has a non-finite coordinate");
+    double vol6 = 0;
+    for (int t = 0; t < nf; ++t) {
+        const double *A = V + 3 * (size_t)F[3 * (size_t)t], *B = V + 3 * (size_t)F[3 * (size_t)t + 1],
+                     *C = V + 3 * (size_t)F[3 * (size_t)t + 2];
+        double u[3], w[3], n[3];
+        sub3(B, A, u); sub3(C, A, w); cross3(u, w, n);
+        if (!(dot3(n, n) > 0.0)) throw Error(ERR_ARG, who + "triangle " + std::to_string(t) + " has zero area");
+        cross3(B, C, n);
+        vol6 += dot3(A, n);
+    }
+    // closed and edge-manifold with consistent orientation: every directed edge once, and its
+    // reverse once
+    std::map<std::pair<int, int>, int> dir;
+    for (int t = 0; t < nf; ++t)
+        for (int a = 0; a < 3; ++a) ++dir[{F[3 * (size_t)t + a], F[3 * (size_t)t + (a + 1) % 3]}];
+    for (int t = 0; t < nf; ++t)
+        for (int a = 0; a < 3; ++a) {
+            const int p = F[3 * (size_t)t + a], q = F[3 * (size_t)t + (a + 1) % 3];
+            const int same = dir[{p, q}];
+            const auto rev_it = dir.find({q, p});
+            const int rev = rev_it == dir.end() ? 0 : rev_it->second;
+            if (same == 1 && rev == 1) continue;
+            const std::string e = "edge (" + std::to_string(p) + ", " + std::to_string(q) + ") of triangle " + std::to_string(t);
+            if (same + rev == 1) throw Error(ERR_ARG, who + e + " lies in one face only: the surface is open");
+            if (same + rev == 2) throw Error(ERR_ARG, who + e + " is run in the same direction by both its faces: inconsistent orientation");
+            throw Error(ERR_ARG, who + e + " lies in " + std::to_string(same + rev) + " faces: the surface is not edge-manifold");
+        }
+    if (!(vol6 > 0.0)) throw Error(ERR_ARG, who + "the signed volume is not positive: the faces must be oriented outward");
+}
+
+// Validates, builds the BVH with the Geometry side's builder and the pseudonormal table.
+inline MeshObstacleHost prepare_mesh_obstacle(const double* V, int nv, const int* F, int nf) {
+    using namespace mesh_detail;
+    validate_mesh_obstacle(V, nv, F, nf);
+    MeshObstacleHost M;
+    BvhBuilder B;
+    B.V = V; B.F = F;
+    B.ids.resize(nf);
+    std::iota(B.ids.begin(), B.ids.end(), 0);
+    B.cen.resize(3 * (size_t)nf);
+    for (int t = 0; t < nf; ++t)
+        for (int d = 0; d < 3; ++d)
+            B.cen[3 * (size_t)t + d] = (V[3 * (size_t)F[3 * t] + d] + V[3 * (size_t)F[3 * t + 1] + d] + V[3 * (size_t)F[3 * t + 2] + d]) / 3.0;
+    B.nodes = &M.nodes;
+    B.tris = &M.tris;
+    M.nodes.reserve(nf);
+    M.tris.reserve(nf);
+    B.build(0, nf);
+    M.orig = B.ids;   // leaves are emitted left to right over ids[b, e): ids is the leaf order
+
+    // unit face normals, then the edge and vertex sums
+    std::vector<double> fn(3 * (size_t)nf), vn(3 * (size_t)nv, 0.0);
+    std::map<std::pair<int, int>, std::array<double, 3>> en;
+    for (int t = 0; t < nf; ++t) {
+        const int id[3] = {F[3 * (size_t)t], F[3 * (size_t)t + 1], F[3 * (size_t)t + 2]};
+        double u[3], w[3], n[3];
+        sub3(V + 3 * (size_t)id[1], V + 3 * (size_t)id[0], u);
+        sub3(V + 3 * (size_t)id[2], V + 3 * (size_t)id[0], w);
+        cross3(u, w, n);
+        const double l = std::sqrt(dot3(n, n));
+        for (int d = 0; d < 3; ++d) fn[3 * (size_t)t + d] = n[d] / l;
+        for (int a = 0; a < 3; ++a) {
+            const int p = id[a], q = id[(a + 1) % 3], r = id[(a + 2) % 3];
+            double e1[3], e2[3];
+            sub3(V + 3 * (size_t)q, V + 3 * (size_t)p, e1);
+            sub3(V + 3 * (size_t)r, V + 3 * (size_t)p, e2);
+            double c = dot3(e1, e2) / std::sqrt(dot3(e1, e1) * dot3(e2, e2));
+            c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
+            const double ang = std::acos(c);
+            auto& E = en[{std::min(p, q), std::max(p, q)}];   // value-initialised to 0 on first use
+            for (int d = 0; d < 3; ++d) {
+                vn[3 * (size_t)p + d] += ang * fn[3 * (size_t)t + d];
+                E[d] += fn[3 * (size_t)t + d];
+            }
+        }
+    }
+    M.pn.resize((size_t)kPnStride * nf);
+    for (int k = 0; k < nf; ++k) {
+        const int t = M.orig[k];
+        const int a = F[3 * (size_t)t], b = F[3 * (size_t)t + 1], c = F[3 * (size_t)t + 2];
+        double* P = M.pn.data() + (size_t)kPnStride * k;
+        auto edge = [&](int p, int q) { return en[{std::min(p, q), std::max(p, q)}].data(); };
+        const double* src[7] = {vn.data() + 3 * (size_t)a, vn.data() + 3 * (size_t)b, edge(a, b), vn.data() + 3 * (size_t)c,
+                                edge(c, a), edge(b, c), fn.data() + 3 * (size_t)t};
+        for (int f = 0; f < 7; ++f)
+            for (int d = 0; d < 3; ++d) P[3 * f + d] = src[f][d];
+    }
+    for (int d = 0; d < 3; ++d) { M.lo[d] = DBL_MAX; M.hi[d] = -DBL_MAX; }
+    for (int t = 0; t < nf; ++t)
+        for (int a = 0; a < 3; ++a)
+            for (int d = 0; d < 3; ++d) {
+                const double v = V[3 * (size_t)F[3 * (size_t)t + a] + d];
+                M.lo[d] = std::min(M.lo[d], v); M.hi[d] = std::max(M.hi[d], v);
+            }
+    return M;
+}
+
+}  // namespace aa

@@ -33,6 +33,7 @@ import numpy as np
 TET, TRI = 0, 1
 # passive obstacles (PassiveObject.hpp:32-136; include/aa_admm.h AA_OBS_*)
 OBS_FLOOR, OBS_SLIDE_FLOOR, OBS_SPHERE, OBS_PLANE_HALF_SPHERE, OBS_CYLINDER = 0, 1, 2, 3, 4
+OBS_MESH = 5   # PassiveMesh (:138-178): Scene.mesh_obstacles / capi.Solver.add_mesh_obstacle
 LINEAR, NEOHOOKEAN, STVK = 0, 1, 2
 VARIANT_X, VARIANT_H = 0, 1  # admm_anderson_xzu (z-AA) / admm_anderson_hard_zxu ((u,x)-AA)
 
@@ -93,6 +94,9 @@ class Scene:
     # [(tris (t, 3) int32, direction (3,))] (Solver::ext_forces)
     obstacles: list = dataclasses.field(default_factory=list)
     collision_idx: Optional[np.ndarray] = None
+    # triangle-mesh obstacles [(V (n, 3), F (m, 3))]: closed, outward-oriented surfaces, added after
+    # `obstacles` in the insertion order (capi.solver_from_scene)
+    mesh_obstacles: list = dataclasses.field(default_factory=list)
     winds: list = dataclasses.field(default_factory=list)
 
     @property
@@ -483,4 +487,63 @@ def windy_cloth(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=3, direction
     sc = cloth(nx, ny, iters=iters, n_steps=n_steps, aa_m=aa_m, accel=accel)
     sc.winds = [(np.asarray(sc.groups[0].idx, np.int32), np.asarray(direction, np.float64))]
     sc.name = f"windycloth{nx}x{ny}"
+    return sc
+
+
+def tet_boundary_faces(verts, tets) -> np.ndarray:
+    """(m, 3) boundary triangles of a tet mesh -- the faces used by exactly one tet -- oriented
+    outward (away from the tet's fourth vertex), in tet order: what a solid tet mesh passes as a
+    mesh obstacle."""
+    verts = np.asarray(verts, np.float64).reshape(-1, 3)
+    tets = np.asarray(tets, np.int64).reshape(-1, 4)
+    loc = np.array([[1, 2, 3], [0, 3, 2], [0, 1, 3], [0, 2, 1]])
+    faces = tets[:, loc].reshape(-1, 3)          # face k of a tet is opposite its vertex k
+    opp = tets.reshape(-1)                        # ... which is opp[4 t + k]
+    _, inv, cnt = np.unique(np.sort(faces, axis=1), axis=0, return_inverse=True, return_counts=True)
+    keep = cnt[inv.reshape(-1)] == 1
+    faces, opp = faces[keep], opp[keep]
+    a, b, c = verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]
+    inward = np.einsum("ij,ij->i", np.cross(b - a, c - a), verts[opp] - a) > 0
+    faces[inward] = faces[inward][:, [0, 2, 1]]
+    return faces.astype(np.int32)
+
+
+def torus_mesh(nu=16, nv=8, R=1.0, r=0.4, center=(0.0, 0.0, 0.0)):
+    """Closed torus surface around the y axis: nu x nv quads split in two, 2 nu nv triangles,
+    oriented outward."""
+    u = 2.0 * np.pi * np.arange(nu) / nu
+    v = 2.0 * np.pi * np.arange(nv) / nv
+    U, Vv = np.meshgrid(u, v, indexing="ij")
+    V = np.stack([(R + r * np.cos(Vv)) * np.cos(U), r * np.sin(Vv), (R + r * np.cos(Vv)) * np.sin(U)], axis=-1).reshape(-1, 3)
+    V = V + np.asarray(center, np.float64)
+    idx = lambda i, j: (i % nu) * nv + (j % nv)
+    F = []
+    for i in range(nu):
+        for j in range(nv):
+            p00, p10, p01, p11 = idx(i, j), idx(i + 1, j), idx(i, j + 1), idx(i + 1, j + 1)
+            F += [(p00, p01, p11), (p00, p11, p10)]
+    return V, np.asarray(F, np.int32)
+
+
+def cloth_on_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15) -> Scene:
+    """Demo of the mesh obstacle: an unpinned cloth sheet dropped flat onto a torus lying in the
+    x-z plane ((u,x) variant; every node collision-checked)."""
+    sc = cloth(nx, ny, variant=VARIANT_H, aa_m=aa_m, iters=iters, n_steps=n_steps, accel=accel)
+    sc.name = "cloth_on_torus"
+    x = np.array(sc.x, np.float64)
+    ext = x.max(0) - x.min(0)
+    flat = np.argsort(ext)[0]                     # lay the sheet in the x-z plane
+    if flat != 1:
+        x[:, [flat, 1]] = x[:, [1, flat]]
+    ctr = 0.5 * (x.max(0) + x.min(0))
+    x = x - ctr
+    R = 0.3 * float(max(ext))
+    r = 0.4 * R
+    x[:, 1] = r + drop
+    sc.x = x
+    sc.pin_idx = np.zeros(0, np.int32)
+    sc.pin_pts = np.zeros((0, 3))
+    sc.pin_vel = np.zeros((0, 3))
+    sc.mesh_obstacles = [torus_mesh(16, 8, R, r)]
+    sc.collision_idx = np.arange(sc.n_nodes, dtype=np.int32)
     return sc

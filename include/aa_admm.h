@@ -122,14 +122,39 @@ int aa_elastic_set_pins(aa_elastic h, const int* inds, const double* points3, in
  * normalised, as the SlideFloor constructor does); SPHERE / PLANE_HALF_SPHERE / CYLINDER
  * {cx,cy,cz, r} (the cylinder's axis is z). The collision terms test every obstacle in insertion
  * order each iteration; obstacles may be added after initialize. The z-AA variant rejects
- * obstacles at initialize (admm_anderson_xzu/src/Solver.cpp:485-489). The BVH mesh obstacle
- * (PassiveMesh) is not provided. */
+ * obstacles at initialize (admm_anderson_xzu/src/Solver.cpp:485-489). The mesh obstacle
+ * (PassiveMesh) has its own call, aa_elastic_add_mesh_obstacle below; AA_OBS_MESH names its type
+ * in obstacle rows and is an "unknown obstacle type" error here. */
 #define AA_OBS_FLOOR 0
 #define AA_OBS_SLIDE_FLOOR 1
 #define AA_OBS_SPHERE 2
 #define AA_OBS_PLANE_HALF_SPHERE 3
 #define AA_OBS_CYLINDER 4
+#define AA_OBS_MESH 5
 int aa_elastic_add_obstacle(aa_elastic h, int type, const double* params);
+/* PassiveMesh (PassiveObject.hpp:138-178): a collision node inside the mesh moves to the nearest
+ * surface point. The obstacle is a closed, edge-manifold, outward-oriented triangle surface
+ * (verts3: 3 n_verts doubles, tris3: 3 n_tris vertex indices). For a candidate q, the closest
+ * surface point c and its triangle are those of the exact fp64 closest-point walk of the
+ * reference-surface constraints (same arithmetic, same tie rule); q is inside iff (q - c) . n < 0
+ * for the angle-weighted pseudonormal n of the feature c lies on (face: the unit face normal; edge:
+ * the sum of the two incident unit face normals; vertex: the sum over incident faces of incident
+ * angle x unit face normal). Inside: dx = -|q - c|, point = c, and -- the reference's rule, whose
+ * PassiveMesh::signed_distance has no `if (dx > p.dx) return;` -- the hit replaces the running
+ * (dx, point) of the obstacles before it unconditionally; obstacles after it compete with their
+ * own test. Not inside: the running payload is left untouched. The obstacle takes its place in
+ * the insertion order shared with aa_elastic_add_obstacle, may be added after initialize (the
+ * step graph is captured again at the next step when it is the first mesh), and is refused by the
+ * z-AA variant at initialize like the analytic ones. *id (optional) receives the mesh's number.
+ * Deviations from the reference, stated: fp64 instead of float, and the boundary surface instead
+ * of point-in-any-tet of a tet mesh (for a solid tet mesh the inside set is the same; pass its
+ * boundary faces). Capacity: AA_MAX_MESH_OBSTACLES meshes per solver (they also count toward the
+ * 256 obstacles in all); one more is AA_ERR_ARG. AA_ERR_ARG with a message naming the first
+ * offending vertex, triangle or edge for: a non-finite coordinate, an index out of range, a
+ * zero-area triangle, an edge not in exactly two faces of opposite directions (open, non-manifold
+ * or inconsistently oriented surfaces), a signed volume that is not positive (inward faces). */
+#define AA_MAX_MESH_OBSTACLES 16
+int aa_elastic_add_mesh_obstacle(aa_elastic h, const double* verts3, int n_verts, const int* tris3, int n_tris, int* id);
 /* Solver::set_collisions(inds, points) (admm_anderson_hard_zxu/src/Solver.cpp:318-344): one
  * Collision energy term (CollisionEnergyTerm.hpp:41-117: identity reduction, weight
  * sqrt(2 k(soft rubber)), prox = closest obstacle surface point when inside one) per listed node,
@@ -317,10 +342,24 @@ int aa_geom_set_comm(aa_geom h, aa_comm c);
  *   aa_test_cod_solve: the Anderson normal-equation solve (Eigen CompleteOrthogonalDecomposition,
  *     AndersonAcceleration.h:186-188) of a k x k column-major M
  *   aa_test_geom_project: Constraint::project_impl of plane (k 3..8) / angle (k 3) / edge (k 2)
- *     on n transformed point sets (3 x cols each, column-major); prm2 = angle min, max / edge length */
+ *     on n transformed point sets (3 x cols each, column-major); prm2 = angle min, max / edge length
+ *   aa_test_mesh_sdf: the mesh obstacle's signed distance on n queries q3: the closest surface
+ *     point, dx (-|q - c| inside; +|q - c| otherwise, reported by this hook only) and the closest
+ *     triangle in the caller's numbering
+ *   aa_test_collision_prox: Collision::prox on n candidates q3 against an obstacle list in
+ *     insertion order: obs_rows = n_obs rows of 8 doubles {type, parameters as stored: a
+ *     SLIDE_FLOOR normal is taken as given}, a row {AA_OBS_MESH, m} naming mesh m of the n_meshes
+ *     meshes given concatenated (mesh m: vertices mesh_vert_ptr[m]..mesh_vert_ptr[m+1] of
+ *     mesh_verts3, triangles mesh_tri_ptr[m]..mesh_tri_ptr[m+1] of mesh_tris3 with indices local
+ *     to the mesh) */
 int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double* in, int n, double* out, int* iters);
 int aa_test_cod_solve(aa_ctx ctx, int k, const double* M, const double* b, double* theta);
 int aa_test_geom_project(aa_ctx ctx, int type, int k, const double* prm2, const double* in, int n, double* out);
+int aa_test_mesh_sdf(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris, const double* q3, int n,
+                     double* closest3, double* dx, int* tri);
+int aa_test_collision_prox(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
+                           const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr, int n_meshes,
+                           const double* q3, int n, double* out3);
 
 #ifdef __cplusplus
 }

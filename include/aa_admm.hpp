@@ -9,6 +9,7 @@
 //   admm::create_tris_from_mesh<float, admm::TriEnergyTerm>(solver.energyterms, verts, inds, n, lame, off);
 //   solver.set_pins(pins, points);                     // Solver::set_pins
 //   solver.add_obstacle(std::make_shared<admm::Floor>(-1.0)); solver.set_collisions(inds);  // (u,x) variant
+//   solver.add_obstacle(std::make_shared<admm::PassiveMesh>(admm::PassiveMesh::from_tets(v, nv, tets, nt)));
 //   solver.ext_forces.push_back(std::make_shared<admm::WindForce>(faces));                    // wind
 //   solver.initialize(settings);                       // Solver::initialize (returns bool)
 //   solver.step();                                     // Solver::step; solver.m_x / m_v updated
@@ -155,6 +156,64 @@ public:
     Cylinder(const Vec3d& c, double r) { type = AA_OBS_CYLINDER; for (int i = 0; i < 3; ++i) params[i] = c[i]; params[3] = r; }
 };
 
+// PassiveMesh (PassiveObject.hpp:138-178): a collision node inside the mesh moves to the nearest
+// surface point. Here the obstacle is a closed, outward-oriented triangle surface (aa_admm.h,
+// aa_elastic_add_mesh_obstacle): built from one directly, or from a tet mesh as the reference's is
+// -- then the boundary faces are taken, the faces used by exactly one tet, oriented outward.
+class PassiveMesh : public PassiveCollision {
+public:
+    std::vector<double> verts;   // 3 per vertex
+    std::vector<int> tris;       // 3 per triangle
+    static PassiveMesh from_surface(const double* verts3, int n_verts, const int* tris3, int n_tris) {
+        PassiveMesh m;
+        m.verts.assign(verts3, verts3 + 3 * (size_t)n_verts);
+        m.tris.assign(tris3, tris3 + 3 * (size_t)n_tris);
+        return m;
+    }
+    static PassiveMesh from_tets(const double* verts3, int n_verts, const int* tets4, int n_tets) {
+        PassiveMesh m;
+        m.verts.assign(verts3, verts3 + 3 * (size_t)n_verts);
+        // face k of a tet lies opposite its vertex k; keyed by its sorted vertex ids
+        static const int loc[4][3] = {{1, 2, 3}, {0, 3, 2}, {0, 1, 3}, {0, 2, 1}};
+        struct Face { std::array<int, 3> key, f; int opp; };
+        std::vector<Face> faces;
+        faces.reserve(4 * (size_t)n_tets);
+        for (int t = 0; t < n_tets; ++t)
+            for (int k = 0; k < 4; ++k) {
+                Face fc;
+                for (int a = 0; a < 3; ++a) fc.f[a] = tets4[4 * (size_t)t + loc[k][a]];
+                fc.key = fc.f;
+                std::sort(fc.key.begin(), fc.key.end());
+                fc.opp = tets4[4 * (size_t)t + k];
+                faces.push_back(fc);
+            }
+        std::vector<int> order(faces.size());
+        for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return faces[a].key < faces[b].key || (faces[a].key == faces[b].key && a < b); });
+        std::vector<char> boundary(faces.size(), 0);
+        for (size_t i = 0; i < order.size();) {
+            size_t j = i + 1;
+            while (j < order.size() && faces[order[j]].key == faces[order[i]].key) ++j;
+            if (j - i == 1) boundary[order[i]] = 1;
+            i = j;
+        }
+        for (size_t i = 0; i < faces.size(); ++i) {   // tet order
+            if (!boundary[i]) continue;
+            Face fc = faces[i];
+            const double *A = verts3 + 3 * (size_t)fc.f[0], *B = verts3 + 3 * (size_t)fc.f[1], *C = verts3 + 3 * (size_t)fc.f[2],
+                         *O = verts3 + 3 * (size_t)fc.opp;
+            const double u[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]}, w[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+            const double n[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};
+            if (n[0] * (O[0] - A[0]) + n[1] * (O[1] - A[1]) + n[2] * (O[2] - A[2]) > 0) std::swap(fc.f[1], fc.f[2]);   // away from the fourth vertex
+            m.tris.insert(m.tris.end(), fc.f.begin(), fc.f.end());
+        }
+        return m;
+    }
+
+private:
+    PassiveMesh() { type = AA_OBS_MESH; }
+};
+
 // Explicit forces (ExplicitForce.hpp:33-47): WindForce on a list of triangles (flat, 3 per face);
 // `direction` may be changed between steps (windyflag.cpp's intensity keys)
 class ExplicitForce {
@@ -225,10 +284,18 @@ public:
     }
 
     // Solver::add_obstacle (Solver.cpp:346-348): takes effect at once, also between steps
-    void add_obstacle(std::shared_ptr<PassiveCollision> obj) { check(aa_elastic_add_obstacle(h_, obj->type, obj->params)); }
+    void add_obstacle(std::shared_ptr<PassiveCollision> obj) {
+        if (const PassiveMesh* m = dynamic_cast<const PassiveMesh*>(obj.get()))
+            check(aa_elastic_add_mesh_obstacle(h_, m->verts.data(), (int)m->verts.size() / 3, m->tris.data(), (int)m->tris.size() / 3, nullptr));
+        else
+            check(aa_elastic_add_obstacle(h_, obj->type, obj->params));
+    }
     // Solver::set_collisions (Solver.cpp:318-344): the points are not used by the prox
+    // Before the first initialize() the device solver has no nodes yet (see below): the list is
+    // kept and handed over with them
     void set_collisions(const std::vector<int>& inds, const std::vector<Vec3>& points = std::vector<Vec3>()) {
         (void)points;
+        if (!bound_) { collisions_ = inds; return; }
         check(aa_elastic_set_collisions(h_, inds.data(), (int)inds.size()));
     }
 
@@ -257,6 +324,7 @@ public:
                 if (rc != AA_OK) return false;
             }
             bound_ = true;
+            if (!collisions_.empty() && aa_elastic_set_collisions(h_, collisions_.data(), (int)collisions_.size()) != AA_OK) return false;
         }
         push_pins();
         aa_settings cs{s.timestep_s, s.verbose, s.admm_iters, s.gravity, s.constraint_w, s.Anderson_m, s.penalty,
@@ -339,7 +407,7 @@ private:
     Settings settings_;
     bool initialized_ = false, bound_ = false;
     VecX x_seen_, v_seen_;
-    std::vector<int> pins_;
+    std::vector<int> pins_, collisions_;
     std::vector<double> pin_pts_;
 };
 
