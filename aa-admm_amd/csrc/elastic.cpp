@@ -502,7 +502,6 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     // on two streams); AA_CONCURRENT=0 keeps it in line
     conc_ = pipe_z_ && !comm_;
     if (const char* e = std::getenv("AA_CONCURRENT")) conc_ = conc_ && e[0] != '0';
-    conc_fork_ = std::getenv("AA_CONC_FORK") ? std::atoi(std::getenv("AA_CONC_FORK")) : 1;
     // u in the parity buffers of the concurrent pass (elastic.hpp); AA_Z_WINDOW=0: u in u_, copied
     // to default_u in the window and restored from it on a reject
     win_u_ = conc_;
@@ -673,14 +672,12 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     if (const char* q = std::getenv("AA_LOCAL_QUEUE")) use_queue_ = q[0] != '0';
     lq_ = make_local_queue(ctx_->device, lzq_.p);
     if (conc_) {
-        lq2_ = make_local_queue(ctx_->device, lzq2_.p);
         // the concurrent pass writes no rhs slots, so it runs the fused refill without their loads
         // (k_local_z_hqf<4, false>: 412 registers, room beside it for the Anderson kernels; the
         // slot-writing form's 452 leave none -- C4 with that on both passes: the main step 25 us
-        // faster, the iteration 100 us slower). Same box, 8 steps: 457.7 / 459.8 -> 459.2 / 464.8
-        // it/s. AA_LQ_FUSED_CONC=0: the plain refill here
-        const char* fc = std::getenv("AA_LQ_FUSED_CONC");
-        lq2_.fused = lq2_.fused && (fc ? fc[0] == '1' : true);
+        // faster, the iteration 100 us slower). Same box, 8 steps: the plain refill in this pass
+        // 457.7 / 459.8 it/s, the fused one 459.2 / 464.8
+        lq2_ = make_local_queue(ctx_->device, lzq2_.p);
     }
     if (const char* q = std::getenv("AA_LQ_STATS"); q && q[0] == '1') {
         lq_stats_.alloc(kLqStats);
@@ -964,26 +961,8 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
     // iteration's Anderson step -- in line on the solver's stream in the instrumented
     // (per-kernel-class timing) pass
     const bool side = pipe && it > 0 && conc_;
-    hipStream_t sst = instrument_ ? s() : side_;
-    // k-1's pass beside this iteration's work: its local step (one wave per SIMD) leaves room for
-    // memory-bound waves beside it. Where it forks (AA_CONC_FORK, same-box A/B on C4): after the
-    // local step (0) 412 / 412 it/s, after the Anderson reduce (1: the reduce then streams at full
-    // occupancy) 415 / 419, after the mix (2) 393 / 396, in line 399 / 400; right after the
-    // two-set solve (-1: the pass's local step would fill the GPU while this iteration's prim check
-    // and gated reject branch -- ~20 launches that exit at once, ~110 us -- go by) 404 / 404 against
-    // 426 / 423: the Anderson step then runs alone, and that overlap was worth more)
-    // (the instrumented pass runs it in line before the Anderson step, outside its timing bracket)
-    auto fork_side = [&](int at) {
-        if (!side || at != (instrument_ ? 0 : conc_fork_)) return;
-        if (sst != s()) {
-            AA_HIP(hipEventRecord(ev_fork_, s()));
-            AA_HIP(hipStreamWaitEvent(sst, ev_fork_, 0));
-        }
-        if (sst == s()) ev_begin("comb");
-        comb_finish_z(CTL_COMB_ZP, sst, ctrl_c_.p, red_c_.p, red_c_.p + nbg_, &lq2_, dup, dzp);
-        if (sst == s()) ev_end("comb");
-        if (sst != s()) AA_HIP(hipEventRecord(ev_join_, sst));
-        join_wait_ = sst != s();
+    auto side_pass = [&](hipStream_t st) {
+        comb_finish_z(CTL_COMB_ZP, st, ctrl_c_.p, red_c_.p, red_c_.p + nbg_, &lq2_, dup, dzp);
     };
     // the working u: u_, or (win_u_) this iteration's default_u buffer itself. Nothing else touches
     // that buffer while this iteration uses it: the pass of iteration it - 2, the last reader of
@@ -1004,7 +983,6 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
         ev_end("solve");
         if (side) {   // the pass's control block: k-1's prim / reject, before this iteration's
             launch_ctrl_fork(c, ctrl_c_.p, s());   // check; its nrej / fail for a rollback
-            fork_side(-1);
         } else {
             ev_begin("comb");
             comb_finish_z(CTL_COMB_ZP, s(), c, pa_, pb_, &lq_, dup, dzp);
@@ -1061,18 +1039,31 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
         ev_begin("local_z");
         local_z_all(xfull_.p, u, dzc, y_.p, LZ_NORMAL, false);
         ev_end("local_z");
-        fork_side(0);
+        if (side && instrument_) {   // the timing pass runs k-1's pass in line, outside the aa bracket
+            ev_begin("comb");
+            side_pass(s());
+            ev_end("comb");
+            join_wait_ = false;
+        }
         Seg2 G{dzc, Z_, nullptr, 0};
         Seg2 out{z_.p, Z_, nullptr, 0};
         Seg2 none{nullptr, 0, nullptr, 0};
         ev_begin("aa");
         launch_aa_reduce(G, z_.p, Z_, aa_dF_.p, aa_dG_.p, c, aa_red_.p, aa_blocks_, none, m, s());
         reduce_aa();
-        fork_side(1);
+        // k-1's pass forks here: its local step (one wave per SIMD) leaves room for memory-bound
+        // waves beside it, and the Anderson reduce, which needs occupancy to stream, is done (the
+        // other fork points measured slower: DESIGN.md §3.4)
+        if (side && !instrument_) {
+            AA_HIP(hipEventRecord(ev_fork_, s()));
+            AA_HIP(hipStreamWaitEvent(side_, ev_fork_, 0));
+            side_pass(side_);
+            AA_HIP(hipEventRecord(ev_join_, side_));
+            join_wait_ = true;
+        }
         if (!instrument_) copy_defaults();
         launch_aa_solve(c, aag_, aa_blocks_, m, s());
         launch_aa_mix(G, z_.p, Z_, aa_dF_.p, aa_dG_.p, c, out, m, s());   // in place (out == cur)
-        fork_side(2);
         ev_end("aa");
         // combined residual "for drawing figures" (Solver.cpp:217-233): extra solve + update_z
         if (pipe) {   // its rhs now (the next iteration overwrites the slots); the rest next iteration

@@ -186,7 +186,6 @@ private:
     // partials and work-queue counter; default_{u,z,x} alternate between two buffers by
     // iteration parity so the pass reads k-1's while iteration k writes its own.
     bool conc_ = false;
-    int conc_fork_ = 1;   // where the side pass forks: after the local step (0), AA reduce (1), mix (2)
     bool join_wait_ = false;
     double* join_dx_ = nullptr;
     void join_side();

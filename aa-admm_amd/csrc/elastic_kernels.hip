@@ -307,9 +307,8 @@ __device__ __forceinline__ int queue_claim(int* queue, int n) {
 // one outer L-BFGS iteration per trip. Each element's arithmetic is unchanged, so the results are
 // bit-identical to k_local_z. This is the plain refill: claim, write the finished elements' z and
 // optional rhs slots, gather the new elements -- each a dependent round trip. Groups with pinned
-// nodes use it (their Cp needs the finished element's positions), as do AA_LQ_FUSED=0 and
-// AA_LQ_FUSED_CONC=0; every other queue launch is k_local_z_hqf below, whose bit-identity
-// baseline this kernel is.
+// nodes use it (their Cp needs the finished element's positions), as does AA_LQ_FUSED=0; every
+// other queue launch is k_local_z_hqf below, whose bit-identity baseline this kernel is.
 template <int NV, class... V>
 __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double* __restrict__ xfull,
                                                        const double* __restrict__ u, double* __restrict__ z,
@@ -1760,7 +1759,7 @@ LocalQueue make_local_queue(int device, int* counter) {
     const char* sp = std::getenv("AA_LQ_SPLIT");
     q.split = sp && sp[0] == '1';   // opt-in: measured slower on C4
     const char* fu = std::getenv("AA_LQ_FUSED");
-    // default on (AA_LQ_FUSED=0: the plain refill); the caller may turn it off for the concurrent pass
+    // default on (AA_LQ_FUSED=0: the plain refill)
     q.fused = (fu ? fu[0] == '1' : true) && !q.split;
     const void* kq = q.fused ? (const void*)k_local_z_hqf<4>
                    : q.split ? (const void*)k_local_z_hq2<4> : (const void*)k_local_z_hq<4>;

@@ -344,26 +344,6 @@ def test_gpu_geom_fused_subtrees_lds_vectors_bit_identical(pkg, ctx, monkeypatch
     assert np.array_equal(a["comb"], b["comb"]) and np.array_equal(a["x"], b["x"]) and ra == rb
 
 
-@pytest.mark.parametrize("builder", [
-    lambda gs: gs.pq_heightfield(40, 36, iters=60, aa_m=10, noise=0.3),   # closeness + planarity
-    lambda gs: gs.wire_grid(40, 40, iters=60, aa_m=20),                   # surface + angle + edge
-])
-def test_gpu_geom_concurrent_groups_bit_identical(builder, pkg, ctx, monkeypatch):
-    """The constraint groups' z / u kernels on parallel graph branches (the closest-point group on
-    the main stream, the others on a side stream; each group writes only its own z, u, rhs slots and
-    residual partial blocks, AA_GEOM_CONCURRENT=1; opt-in, measured slower) give bit-identical
-    trajectories to one stream (the default)."""
-    sc = builder(pkg.geom_scenes)
-    runs = []
-    for conc in ("0", "1"):
-        monkeypatch.setenv("AA_GEOM_CONCURRENT", conc)
-        h, g = pkg.capi.run_geom(ctx, sc)
-        runs.append((h, g.runtime().rejects))
-        g.close()
-    (a, ra), (b, rb) = runs
-    assert np.array_equal(a["comb"], b["comb"]) and np.array_equal(a["x"], b["x"]) and ra == rb
-
-
 def test_gpu_c3_eps_regime_matches_reference(pkg, ctx):
     """C3's run-to-epsilon pinned to the reference past the crossing: the full
     PQ 317 x 317 scene (m = 10), 1 500 accepted iterations without a stop, against the reference's
