@@ -24,7 +24,8 @@ EXPORTS = [
     "aa_ctx_warm_dense", "aa_lame_from_young",
     "aa_settings_default", "aa_elastic_create", "aa_elastic_destroy", "aa_elastic_add_nodes", "aa_elastic_add_tets",
     "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
-    "aa_elastic_add_obstacle", "aa_elastic_add_mesh_obstacle", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
+    "aa_elastic_add_obstacle", "aa_elastic_add_mesh_obstacle", "aa_elastic_set_mesh_obstacle_pose",
+    "aa_elastic_get_mesh_obstacle_pose", "aa_elastic_num_obstacles", "aa_elastic_set_obstacle", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
     "aa_elastic_num_nodes", "aa_elastic_get_x", "aa_elastic_get_v", "aa_elastic_set_v", "aa_elastic_get_history",
     "aa_elastic_get_times", "aa_elastic_set_iterations", "aa_elastic_set_x",
     "aa_elastic_runtime", "aa_elastic_bench_iterations", "aa_elastic_kernel_stats", "aa_elastic_local_stats",
@@ -35,6 +36,7 @@ EXPORTS = [
     "aa_geom_add_closeness", "aa_geom_add_laplacians", "aa_geom_add_closenesses", "aa_geom_setup", "aa_geom_solve", "aa_geom_set_stop", "aa_geom_get_solution", "aa_geom_get_history",
     "aa_geom_runtime_info", "aa_geom_closest_points", "aa_geom_bench_iterations", "aa_geom_kernel_stats",
     "aa_test_prox", "aa_test_cod_solve", "aa_test_geom_project", "aa_test_mesh_sdf", "aa_test_collision_prox",
+    "aa_test_mesh_sdf_posed", "aa_test_collision_prox_posed",
 ]
 
 # Geometry constraint types (Geometry/Constraint.h) and SPD solver types (SolverCommon.h)
@@ -355,6 +357,39 @@ class Solver:
                                                 C.byref(k)))
         return k.value
 
+    def set_mesh_obstacle_pose(self, mesh_id, R=None, t=None):
+        """A mesh obstacle's rigid pose for every later step: the surface seen is R v + t for the
+        vertices v it was added with (R (3, 3) a rotation, used as given). R None: back to unposed.
+        One table row is written; nothing is rebuilt and the captured step graph is kept."""
+        if R is None:
+            _chk(lib().aa_elastic_set_mesh_obstacle_pose(self.h, C.c_int(mesh_id), None))
+            return
+        _chk(lib().aa_elastic_set_mesh_obstacle_pose(self.h, C.c_int(mesh_id), _dp(pose12(R, t))))
+
+    def mesh_obstacle_pose(self, mesh_id):
+        """(R, t, posed) of a mesh obstacle: the pose in force (identity when unposed)."""
+        p = np.zeros(12)
+        posed = C.c_int()
+        _chk(lib().aa_elastic_get_mesh_obstacle_pose(self.h, C.c_int(mesh_id), _dp(p), C.byref(posed)))
+        return p[:9].reshape(3, 3).copy(), p[9:].copy(), bool(posed.value)
+
+    def num_obstacles(self):
+        """Obstacle rows, analytic and mesh, in the shared insertion order."""
+        n = C.c_int()
+        _chk(lib().aa_elastic_num_obstacles(self.h, C.byref(n)))
+        return n.value
+
+    def set_obstacle(self, index, kind, params):
+        """Re-parameterises the analytic obstacle at `index` of the insertion order (add_obstacle's
+        parameter layout); `kind` must be the row's stored type."""
+        if params is None:
+            _chk(lib().aa_elastic_set_obstacle(self.h, C.c_int(index), C.c_int(kind), None))
+            return
+        p = np.zeros(8)
+        q = np.asarray(params, np.float64).reshape(-1)
+        p[:len(q)] = q
+        _chk(lib().aa_elastic_set_obstacle(self.h, C.c_int(index), C.c_int(kind), _dp(p)))
+
     def set_collisions(self, inds):
         i = np.ascontiguousarray(inds, np.int32).reshape(-1)
         _chk(lib().aa_elastic_set_collisions(self.h, _ip(i), C.c_int(len(i))))
@@ -469,6 +504,22 @@ class Solver:
         return dict(hist=out[:101].copy(), trips=int(out[101]), refills=int(out[102]), waves=int(out[103]))
 
 
+def pose12(R, t=None):
+    """R (3, 3) and t (3,) as the 12 doubles of aa_elastic_set_mesh_obstacle_pose: R row-major, then t."""
+    p = np.zeros(12)
+    p[:9] = np.asarray(R, np.float64).reshape(9)
+    if t is not None:
+        p[9:] = np.asarray(t, np.float64).reshape(3)
+    return p
+
+
+def _pose_arg(pose):
+    """A pose given as (R, t) or as 12 doubles."""
+    if isinstance(pose, (tuple, list)) and len(pose) == 2:
+        return pose12(pose[0], pose[1])
+    return np.ascontiguousarray(pose, np.float64).reshape(12).copy()
+
+
 def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
     """Binds a scenes.Scene the way binding::add_trimesh/add_tetmesh + the samples do."""
     s = Solver(ctx)
@@ -517,6 +568,11 @@ def run_scene(ctx: Context, scene, n_steps=None, comm=None):
     for k in range(1, n_steps + 1):
         if np.any(scene.pin_vel != 0):
             s.set_pins(scene.pin_idx, scene.pin_pts + k * scene.pin_vel)
+        poses = getattr(scene, "mesh_obstacle_poses", None)
+        if poses is not None:   # kinematic obstacles: step k runs against row k - 1 (the last row holds on)
+            row = np.asarray(poses, np.float64)[min(k, len(poses)) - 1]
+            for m in range(row.shape[0]):
+                s.set_mesh_obstacle_pose(m, row[m, :9].reshape(3, 3), row[m, 9:])
         s.step()
         h = s.history()
         h["x"], h["v"] = s.x, s.v
@@ -769,22 +825,28 @@ def hook_geom_project(ctx: Context, ctype, k, params, P):
     return out
 
 
-def hook_mesh_sdf(ctx: Context, V, F, Q):
+def hook_mesh_sdf(ctx: Context, V, F, Q, pose=None):
     """The mesh obstacle's signed distance on queries Q (n, 3): (closest points, dx, triangle) with
-    dx = -|q - c| inside and +|q - c| otherwise, the triangle in F's numbering."""
+    dx = -|q - c| inside and +|q - c| otherwise, the triangle in F's numbering. pose = (R, t) or 12
+    doubles: the obstacle posed (Q and the closest points in the world frame)."""
     v = np.ascontiguousarray(V, np.float64).reshape(-1)
     f = np.ascontiguousarray(F, np.int32).reshape(-1)
     q = np.ascontiguousarray(Q, np.float64).reshape(-1, 3)
     n = q.shape[0]
     c, dx, tri = np.zeros((n, 3)), np.zeros(n), np.zeros(n, np.int32)
+    if pose is not None:
+        _chk(lib().aa_test_mesh_sdf_posed(ctx.h, _dp(v), C.c_int(len(v) // 3), _ip(f), C.c_int(len(f) // 3),
+                                          _dp(_pose_arg(pose)), _dp(q), C.c_int(n), _dp(c), _dp(dx), _ip(tri)))
+        return c, dx, tri
     _chk(lib().aa_test_mesh_sdf(ctx.h, _dp(v), C.c_int(len(v) // 3), _ip(f), C.c_int(len(f) // 3), _dp(q), C.c_int(n),
                                 _dp(c), _dp(dx), _ip(tri)))
     return c, dx, tri
 
 
-def hook_collision_prox(ctx: Context, obstacles, meshes, Q):
+def hook_collision_prox(ctx: Context, obstacles, meshes, Q, poses=None):
     """Collision::prox of candidates Q (n, 3) against `obstacles` in insertion order: (type, params)
-    pairs, a mesh as (AA_OBS_MESH, [m]) naming meshes[m] = (V, F)."""
+    pairs, a mesh as (AA_OBS_MESH, [m]) naming meshes[m] = (V, F). poses: one entry per mesh, (R, t)
+    or 12 doubles, None for an unposed mesh."""
     rows = np.zeros((len(obstacles), 8))
     for k, (kind, prm) in enumerate(obstacles):
         a = np.asarray(prm, np.float64).reshape(-1)
@@ -798,6 +860,17 @@ def hook_collision_prox(ctx: Context, obstacles, meshes, Q):
     ff = np.ascontiguousarray(np.concatenate(fs) if fs else np.zeros((1, 3), np.int32))
     q = np.ascontiguousarray(Q, np.float64).reshape(-1, 3)
     out = np.zeros_like(q)
+    if poses is not None:
+        if len(poses) != len(meshes):
+            raise ValueError("hook_collision_prox: one pose (or None) per mesh")
+        pp = np.full((max(len(meshes), 1), 12), np.nan)   # a row of NaNs: that mesh unposed
+        for m, p in enumerate(poses):
+            if p is not None:
+                pp[m] = _pose_arg(p)
+        _chk(lib().aa_test_collision_prox_posed(ctx.h, _dp(rows), C.c_int(len(obstacles)), _dp(vv), _ip(vptr), _ip(ff),
+                                                _ip(fptr), C.c_int(len(meshes)), _dp(pp), _dp(q), C.c_int(q.shape[0]),
+                                                _dp(out)))
+        return out
     _chk(lib().aa_test_collision_prox(ctx.h, _dp(rows), C.c_int(len(obstacles)), _dp(vv), _ip(vptr), _ip(ff), _ip(fptr),
                                       C.c_int(len(meshes)), _dp(q), C.c_int(q.shape[0]), _dp(out)))
     return out

@@ -57,12 +57,18 @@ struct SurfDev {
 // (kPnStride doubles each: 7 features x 3, indexed by closest_on_tri's region code), the
 // leaf-order -> caller's triangle index map and the root box in fp64 (the exact range of the
 // vertices: a point outside it is not inside the surface).
+// Kinematic obstacles: a rigid pose per row, world = R * local + t (R row-major, obstacle frame ->
+// world). Everything above stays in the obstacle frame as uploaded; a posed row's candidate is
+// taken into that frame, walked there, and the closest point taken back (device_prox.hpp).
+// posed = 0: the row is read as before the pose existed (R, t are not looked at).
 constexpr int kPnStride = 21;
 struct MeshObsDev {
     SurfDev surf;
     const double* pn;
     const int* orig;
     double lo[3], hi[3];
+    double R[9], t[3];
+    int posed;
 };
 
 }  // namespace aa

@@ -200,6 +200,34 @@ int aa_elastic_add_mesh_obstacle(aa_elastic h, const double* verts3, int n_verts
     });
 }
 
+int aa_elastic_set_mesh_obstacle_pose(aa_elastic h, int mesh_id, const double pose12[12]) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
+        h->s->set_mesh_obstacle_pose(mesh_id, pose12);
+    });
+}
+
+int aa_elastic_get_mesh_obstacle_pose(aa_elastic h, int mesh_id, double pose12[12], int* posed) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        const bool p = h->s->mesh_obstacle_pose(mesh_id, pose12);
+        if (posed) *posed = p ? 1 : 0;
+    });
+}
+
+int aa_elastic_num_obstacles(aa_elastic h, int* n) {
+    return guarded([&] { NEED(h && n, "null argument"); *n = h->s->num_obstacles(); });
+}
+
+int aa_elastic_set_obstacle(aa_elastic h, int index, int type, const double* params) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
+        h->s->set_obstacle(index, type, params);
+    });
+}
+
 int aa_elastic_set_collisions(aa_elastic h, const int* inds, int n) {
     return guarded([&] { NEED(h, "null handle"); h->s->set_collisions(inds, n); });
 }
@@ -551,11 +579,19 @@ extern "C" int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double
 
 extern "C" int aa_test_mesh_sdf(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
                                const double* q3, int n, double* closest3, double* dx, int* tri) {
+    return aa_test_mesh_sdf_posed(ctx, verts3, n_verts, tris3, n_tris, nullptr, q3, n, closest3, dx, tri);
+}
+
+extern "C" int aa_test_mesh_sdf_posed(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
+                                     const double* pose12, const double* q3, int n, double* closest3, double* dx,
+                                     int* tri) {
     return with_device_arrays(ctx, [&](hipStream_t s) {
         NEED(q3 && closest3 && dx && tri && n >= 0, "aa_test_mesh_sdf: bad argument");
         const aa::MeshObstacleHost M = aa::prepare_mesh_obstacle(verts3, n_verts, tris3, n_tris);
+        if (pose12) aa::validate_mesh_pose(pose12, "aa_test_mesh_sdf_posed: ");
         aa::MeshObsBuffers buf;
-        const aa::MeshObsDev d = buf.upload(M, s);
+        aa::MeshObsDev d = buf.upload(M, s);
+        aa::apply_mesh_pose(d, pose12);
         aa::DevBuf<aa::MeshObsDev> dd;
         dd.upload(&d, 1, s);
         aa::DevBuf<double> dq, dc((size_t)3 * std::max(n, 1)), ddx(std::max(n, 1));
@@ -572,6 +608,14 @@ extern "C" int aa_test_mesh_sdf(aa_ctx ctx, const double* verts3, int n_verts, c
 extern "C" int aa_test_collision_prox(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
                                      const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr,
                                      int n_meshes, const double* q3, int n, double* out3) {
+    return aa_test_collision_prox_posed(ctx, obs_rows, n_obs, mesh_verts3, mesh_vert_ptr, mesh_tris3, mesh_tri_ptr,
+                                        n_meshes, nullptr, q3, n, out3);
+}
+
+extern "C" int aa_test_collision_prox_posed(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
+                                           const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr,
+                                           int n_meshes, const double* mesh_poses, const double* q3, int n,
+                                           double* out3) {
     return with_device_arrays(ctx, [&](hipStream_t s) {
         NEED(q3 && out3 && n >= 0 && n_obs >= 0 && n_obs <= aa::kMaxObstacles && (obs_rows || n_obs == 0),
              "aa_test_collision_prox: bad argument");
@@ -585,6 +629,10 @@ extern "C" int aa_test_collision_prox(aa_ctx ctx, const double* obs_rows, int n_
                 mesh_tris3 + 3 * (size_t)mesh_tri_ptr[m], mesh_tri_ptr[m + 1] - mesh_tri_ptr[m]);
             bufs.push_back(std::make_unique<aa::MeshObsBuffers>());
             table[m] = bufs.back()->upload(M, s);
+            const double* pose = mesh_poses ? mesh_poses + 12 * (size_t)m : nullptr;
+            if (pose && std::all_of(pose, pose + 12, [](double v) { return std::isnan(v); })) pose = nullptr;   // this mesh unposed
+            if (pose) aa::validate_mesh_pose(pose, "aa_test_collision_prox_posed: ");
+            aa::apply_mesh_pose(table[m], pose);
         }
         std::vector<double> h(1 + (size_t)aa::kObsStride * n_obs, 0.0);
         h[0] = n_obs;

@@ -252,10 +252,29 @@ __device__ inline bool mesh_in_root_box(const MeshObsDev& mo, const double* q) {
     return q[0] >= mo.lo[0] && q[0] <= mo.hi[0] && q[1] >= mo.lo[1] && q[1] <= mo.hi[1] && q[2] >= mo.lo[2] &&
            q[2] <= mo.hi[2];
 }
+// Kinematic rows (mo.posed, a wave-uniform branch: every lane reads the same row): the candidate
+// goes into the obstacle frame, q_l = R^T (q - t), everything above runs there on q_l -- the cull
+// after the transform, so a culled lane is still masked off for the whole walk -- and the closest
+// point comes back, c_w = R c_l + t. The operation order is fixed (no contraction, sums left to
+// right) so that a host restatement gives the same bits. dx is the obstacle-frame distance.
+// An unposed row runs the arithmetic it always did.
+__device__ inline void mesh_to_local(const MeshObsDev& mo, const double* q, double* ql) {
+#pragma clang fp contract(off)
+    const double d0 = q[0] - mo.t[0], d1 = q[1] - mo.t[1], d2 = q[2] - mo.t[2];
+    for (int i = 0; i < 3; ++i) ql[i] = (mo.R[i] * d0 + mo.R[3 + i] * d1) + mo.R[6 + i] * d2;
+}
+__device__ inline void mesh_to_world(const MeshObsDev& mo, const double* cl, double* c) {
+#pragma clang fp contract(off)
+    const double c0 = cl[0], c1 = cl[1], c2 = cl[2];
+    for (int i = 0; i < 3; ++i) c[i] = ((mo.R[3 * i] * c0 + mo.R[3 * i + 1] * c1) + mo.R[3 * i + 2] * c2) + mo.t[i];
+}
 __device__ inline bool mesh_signed_distance(const MeshObsDev& mo, const double* q, double& dx, double* c, int& tri) {
-    if (!mesh_in_root_box(mo, q)) return false;
-    if (!(mesh_closest_signed(mo, q, c, tri) < 0.0)) return false;
-    dx = -sqrt(dist2(q[0], q[1], q[2], c[0], c[1], c[2]));
+    double ql[3] = {q[0], q[1], q[2]};
+    if (mo.posed) mesh_to_local(mo, q, ql);
+    if (!mesh_in_root_box(mo, ql)) return false;
+    if (!(mesh_closest_signed(mo, ql, c, tri) < 0.0)) return false;
+    dx = -sqrt(dist2(ql[0], ql[1], ql[2], c[0], c[1], c[2]));
+    if (mo.posed) mesh_to_world(mo, c, c);
     return true;
 }
 __device__ __forceinline__ const MeshObsDev* mesh_table_of(const MeshObsDev* t) { return t; }

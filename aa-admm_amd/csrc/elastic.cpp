@@ -159,10 +159,7 @@ void ElasticSolver::HostGroup::append_element(const HostGroup& from, size_t t) {
 // PassiveObject.hpp:32-136. The collision terms read the obstacle table every iteration, so
 // obstacles may be added after initialize (as in the reference, whose prox walks the collider's
 // list each time).
-void ElasticSolver::add_obstacle(int type, const double* prm) {
-    if (!prm) throw Error(ERR_ARG, "add_obstacle: null parameters");
-    if (type < OBS_FLOOR || type > OBS_CYLINDER) throw Error(ERR_ARG, "add_obstacle: unknown obstacle type");
-    if ((int)obstacles_.size() >= kMaxObstacles) throw Error(ERR_ARG, "add_obstacle: too many obstacles");
+static std::array<double, kObsStride> obstacle_row(int type, const double* prm) {
     std::array<double, kObsStride> o{};
     o[0] = type;
     const int np = type == OBS_FLOOR ? 1 : (type == OBS_SLIDE_FLOOR ? 6 : 4);
@@ -171,8 +168,53 @@ void ElasticSolver::add_obstacle(int type, const double* prm) {
         const double z2 = (o[4] * o[4] + o[5] * o[5]) + o[6] * o[6];
         if (z2 > 0.0) { const double nr = std::sqrt(z2); o[4] /= nr; o[5] /= nr; o[6] /= nr; }
     }
-    obstacles_.push_back(o);
+    return o;
+}
+
+void ElasticSolver::add_obstacle(int type, const double* prm) {
+    if (!prm) throw Error(ERR_ARG, "add_obstacle: null parameters");
+    if (type < OBS_FLOOR || type > OBS_CYLINDER) throw Error(ERR_ARG, "add_obstacle: unknown obstacle type");
+    if ((int)obstacles_.size() >= kMaxObstacles) throw Error(ERR_ARG, "add_obstacle: too many obstacles");
+    obstacles_.push_back(obstacle_row(type, prm));
     if (initialized_) upload_obstacles();
+}
+
+// A moving analytic obstacle: the row's parameters replaced where it stands (the table's address
+// and length do not change, so neither does the captured graph).
+void ElasticSolver::set_obstacle(int index, int type, const double* prm) {
+    if (index < 0 || index >= (int)obstacles_.size())
+        throw Error(ERR_ARG, "set_obstacle: index " + std::to_string(index) + " out of range (" + std::to_string(obstacles_.size()) + " obstacles)");
+    const int have = (int)obstacles_[index][0];
+    if (have == OBS_MESH) throw Error(ERR_ARG, "set_obstacle: obstacle " + std::to_string(index) + " is a mesh (use set_mesh_obstacle_pose)");
+    if (type != have)
+        throw Error(ERR_ARG, "set_obstacle: type mismatch at obstacle " + std::to_string(index) + ": stored type " + std::to_string(have) + ", given " + std::to_string(type));
+    if (!prm) throw Error(ERR_ARG, "set_obstacle: null parameters");
+    const int np = type == OBS_FLOOR ? 1 : (type == OBS_SLIDE_FLOOR ? 6 : 4);
+    for (int k = 0; k < np; ++k)
+        if (!std::isfinite(prm[k])) throw Error(ERR_ARG, "set_obstacle: parameter " + std::to_string(k) + " is not finite");
+    obstacles_[index] = obstacle_row(type, prm);
+    if (initialized_) upload_obstacles();
+}
+
+void ElasticSolver::set_mesh_obstacle_pose(int mesh_id, const double* pose12) {
+    if (mesh_id < 0 || mesh_id >= (int)meshes_.size())
+        throw Error(ERR_ARG, "set_mesh_obstacle_pose: unknown mesh id " + std::to_string(mesh_id) + " (" + std::to_string(meshes_.size()) + " meshes)");
+    if (pose12) validate_mesh_pose(pose12, "set_mesh_obstacle_pose: ");
+    MeshObsDev& d = mesh_rows_[mesh_id];
+    apply_mesh_pose(d, pose12);
+    AA_HIP(hipMemcpyAsync(mesh_dev_.p + mesh_id, &d, sizeof(d), hipMemcpyHostToDevice, s()));
+    AA_HIP(hipStreamSynchronize(s()));
+}
+
+bool ElasticSolver::mesh_obstacle_pose(int mesh_id, double* pose12) const {
+    if (mesh_id < 0 || mesh_id >= (int)meshes_.size())
+        throw Error(ERR_ARG, "get_mesh_obstacle_pose: unknown mesh id " + std::to_string(mesh_id) + " (" + std::to_string(meshes_.size()) + " meshes)");
+    const MeshObsDev& d = mesh_rows_[mesh_id];
+    if (pose12) {
+        for (int i = 0; i < 9; ++i) pose12[i] = d.R[i];
+        for (int i = 0; i < 3; ++i) pose12[9 + i] = d.t[i];
+    }
+    return d.posed != 0;
 }
 
 // PassiveMesh: validated and prepared on the host (mesh_obstacle.hpp), uploaded here, and entered
@@ -185,12 +227,14 @@ int ElasticSolver::add_mesh_obstacle(const double* V3, int nv, const int* F3, in
         throw Error(ERR_ARG, "add_mesh_obstacle: too many mesh obstacles (at most " + std::to_string(kMaxMeshObstacles) + ")");
     const MeshObstacleHost M = prepare_mesh_obstacle(V3, nv, F3, nf);
     auto mo = std::make_unique<MeshObsBuffers>();
-    const MeshObsDev d = mo->upload(M, s());
+    MeshObsDev d = mo->upload(M, s());
+    apply_mesh_pose(d, nullptr);
     if (!mesh_dev_.p) mesh_dev_.alloc(kMaxMeshObstacles);
     const int row = (int)meshes_.size();
     AA_HIP(hipMemcpyAsync(mesh_dev_.p + row, &d, sizeof(d), hipMemcpyHostToDevice, s()));
     AA_HIP(hipStreamSynchronize(s()));
     meshes_.push_back(std::move(mo));
+    mesh_rows_.push_back(d);
     std::array<double, kObsStride> o{};
     o[0] = OBS_MESH;
     o[1] = row;

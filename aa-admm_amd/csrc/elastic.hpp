@@ -57,6 +57,14 @@ public:
     // PassiveMesh (PassiveObject.hpp:138-178) as a closed triangle surface (mesh_obstacle.hpp);
     // takes its place in add_obstacle's insertion order. Returns the mesh's row in the table.
     int add_mesh_obstacle(const double* verts3, int n_verts, const int* tris3, int n_tris);
+    // Kinematic obstacles. A mesh's rigid pose (R row-major then t, null = unposed) for every
+    // later iteration: one row of the device mesh table rewritten on the solver's stream, which
+    // the captured graph reads at replay, so the graph stays. An analytic row re-parameterised in
+    // place (index in the shared insertion order; type must match the stored one).
+    void set_mesh_obstacle_pose(int mesh_id, const double* pose12);
+    bool mesh_obstacle_pose(int mesh_id, double* pose12) const;
+    int num_obstacles() const { return (int)obstacles_.size(); }
+    void set_obstacle(int index, int type, const double* params);
     // WindForce (ExplicitForce.hpp:39-47) on the given triangles; returns its id
     int add_wind(const int* tris3, int ntris, const double* dir3);
     void set_wind(int id, const double* dir3);
@@ -127,6 +135,7 @@ private:
     // so a captured graph stays valid when a later mesh fills another row)
     std::vector<std::unique_ptr<MeshObsBuffers>> meshes_;
     DevBuf<MeshObsDev> mesh_dev_;
+    std::vector<MeshObsDev> mesh_rows_;   // the table's rows as last written
     const MeshObsDev* mesh_table(const GroupDev& d) const { return d.kind == 2 && !meshes_.empty() ? mesh_dev_.p : nullptr; }
     void build_wind(Wind& w);
     std::vector<int> pin_order_;

@@ -1712,9 +1712,12 @@ __global__ __launch_bounds__(kBlock) void k_test_mesh_sdf(const MeshObsDev* __re
     const double p[3] = {q[3 * (size_t)e], q[3 * (size_t)e + 1], q[3 * (size_t)e + 2]};
     double c[3], d = 0.0;
     int t = -1;
-    if (!dev::mesh_signed_distance(mo, p, d, c, t)) {
-        dev::mesh_closest_signed(mo, p, c, t);
-        d = sqrt(dist2(p[0], p[1], p[2], c[0], c[1], c[2]));
+    if (!dev::mesh_signed_distance(mo, p, d, c, t)) {   // a posed row: walked in its frame, c reported in the world's
+        double pl[3] = {p[0], p[1], p[2]};
+        if (mo.posed) dev::mesh_to_local(mo, p, pl);
+        dev::mesh_closest_signed(mo, pl, c, t);
+        d = sqrt(dist2(pl[0], pl[1], pl[2], c[0], c[1], c[2]));
+        if (mo.posed) dev::mesh_to_world(mo, c, c);
     }
     for (int i = 0; i < 3; ++i) closest[3 * (size_t)e + i] = c[i];
     dx[e] = d;

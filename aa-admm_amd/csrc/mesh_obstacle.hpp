@@ -90,6 +90,30 @@ inline void validate_mesh_obstacle(const double* V, int nv, const int* F, int nf
     if (!(vol6 > 0.0)) throw Error(ERR_ARG, who + "the signed volume is not positive: the faces must be oriented outward");
 }
 
+// A kinematic obstacle's rigid pose, pose12 = R (row-major 3x3, obstacle frame -> world) then t.
+// R is used as given, so it has to be a rotation already: throws Error(ERR_ARG) naming the cause
+// for a non-finite entry, max|R^T R - I| > 1e-12, or det R <= 0 (a reflection would turn the
+// surface inside out).
+inline void validate_mesh_pose(const double* p, const std::string& who) {
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(p[i])) throw Error(ERR_ARG, who + "pose entry " + std::to_string(i) + " is not finite");
+    double dev = 0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double g = p[i] * p[j] + p[3 + i] * p[3 + j] + p[6 + i] * p[6 + j];
+            dev = std::max(dev, std::fabs(g - (i == j ? 1.0 : 0.0)));
+        }
+    if (dev > 1e-12) throw Error(ERR_ARG, who + "R is not orthonormal: max|R^T R - I| = " + std::to_string(dev) + " > 1e-12");
+    const double det = p[0] * (p[4] * p[8] - p[5] * p[7]) - p[1] * (p[3] * p[8] - p[5] * p[6]) + p[2] * (p[3] * p[7] - p[4] * p[6]);
+    if (!(det > 0.0)) throw Error(ERR_ARG, who + "det R <= 0: a reflection would turn the surface inside out");
+}
+// The pose (null = unposed) written into a table row
+inline void apply_mesh_pose(MeshObsDev& d, const double* pose12) {
+    d.posed = pose12 ? 1 : 0;
+    for (int i = 0; i < 9; ++i) d.R[i] = pose12 ? pose12[i] : (i % 4 == 0 ? 1.0 : 0.0);
+    for (int i = 0; i < 3; ++i) d.t[i] = pose12 ? pose12[9 + i] : 0.0;
+}
+
 // Validates, builds the BVH with the Geometry side's builder and the pseudonormal table.
 inline MeshObstacleHost prepare_mesh_obstacle(const double* V, int nv, const int* F, int nf) {
     using namespace mesh_detail;

@@ -97,6 +97,10 @@ class Scene:
     # triangle-mesh obstacles [(V (n, 3), F (m, 3))]: closed, outward-oriented surfaces, added after
     # `obstacles` in the insertion order (capi.solver_from_scene)
     mesh_obstacles: list = dataclasses.field(default_factory=list)
+    # kinematic mesh obstacles: (n_steps, n_meshes, 12) rigid poses, R row-major (obstacle frame ->
+    # world) then t; the scene runner sets row k - 1 before step k, where it advances the moving
+    # pins (capi.run_scene). None = the meshes stay as given.
+    mesh_obstacle_poses: Optional[np.ndarray] = None
     winds: list = dataclasses.field(default_factory=list)
 
     @property
@@ -546,4 +550,22 @@ def cloth_on_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=
     sc.pin_vel = np.zeros((0, 3))
     sc.mesh_obstacles = [torus_mesh(16, 8, R, r)]
     sc.collision_idx = np.arange(sc.n_nodes, dtype=np.int32)
+    return sc
+
+
+def rotation_y(angle: float) -> np.ndarray:
+    """Rotation by `angle` about the y axis (3, 3)."""
+    c, s = np.cos(angle), np.sin(angle)
+    return np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])
+
+
+def cloth_on_spinning_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15, dtheta=0.05) -> Scene:
+    """Demo of the kinematic mesh obstacle: cloth_on_torus with the torus turning about the y axis
+    by `dtheta` per step (step k runs against the torus turned by k dtheta)."""
+    sc = cloth_on_torus(nx, ny, iters=iters, aa_m=aa_m, accel=accel, n_steps=n_steps, drop=drop)
+    sc.name = "cloth_on_spinning_torus"
+    poses = np.zeros((n_steps, 1, 12))
+    for k in range(n_steps):
+        poses[k, 0, :9] = rotation_y((k + 1) * dtheta).reshape(9)
+    sc.mesh_obstacle_poses = poses
     return sc

@@ -155,6 +155,35 @@ int aa_elastic_add_obstacle(aa_elastic h, int type, const double* params);
  * or inconsistently oriented surfaces), a signed volume that is not positive (inward faces). */
 #define AA_MAX_MESH_OBSTACLES 16
 int aa_elastic_add_mesh_obstacle(aa_elastic h, const double* verts3, int n_verts, const int* tris3, int n_tris, int* id);
+/* Kinematic obstacles: a rigid pose per mesh obstacle, changed as often as every step at the cost
+ * of one table row (no re-validation, no BVH work, no new mesh row). pose12 = R (row-major 3x3,
+ * obstacle frame -> world) then t: the surface the collision terms see is R v + t for the vertices
+ * v given to aa_elastic_add_mesh_obstacle, which stay as uploaded. NULL = back to unposed. The
+ * candidate q is taken into the obstacle frame, tested there by the unchanged walk, and the closest
+ * point taken back, in this fixed operation order (no FMA contraction):
+ *   d = q - t;  q_l[i] = (R[0][i] d0 + R[1][i] d1) + R[2][i] d2;
+ *   root-box cull, closest point c_l, pseudonormal sign and dx = -|q_l - c_l| on q_l;
+ *   c_w[i] = ((R[i][0] c0 + R[i][1] c1) + R[i][2] c2) + t[i].
+ * A mesh that never had a pose set takes exactly the unposed arithmetic. May be called before or
+ * after initialize and between steps; it writes the mesh's row of the device table on the solver's
+ * stream and keeps the captured step graph. The pose holds for every ADMM iteration of every later
+ * step until changed. The obstacle is kinematic: it has no velocity and exerts no friction; a node
+ * it overruns is moved to its surface by the next step's prox. R is used as given (no
+ * re-orthonormalisation). AA_ERR_ARG, the message naming the cause: an unknown mesh_id, a
+ * non-finite entry, max|R^T R - I| > 1e-12, det R <= 0 (a reflection would turn the surface
+ * inside out). Partitioned solvers: every rank makes the same call, as for add_obstacle.
+ * aa_elastic_get_mesh_obstacle_pose returns the pose in force (identity when unposed) and whether
+ * one is set; either output may be NULL. */
+int aa_elastic_set_mesh_obstacle_pose(aa_elastic h, int mesh_id, const double pose12[12]);
+int aa_elastic_get_mesh_obstacle_pose(aa_elastic h, int mesh_id, double pose12[12], int* posed);
+/* The number of obstacle rows, analytic and mesh, in the shared insertion order. */
+int aa_elastic_num_obstacles(aa_elastic h, int* n);
+/* Re-parameterises the analytic obstacle at position `index` of that order (a rising floor, a
+ * rolling sphere): parameter layout and SLIDE_FLOOR normalisation of aa_elastic_add_obstacle; the
+ * new parameters hold from the next step on; before or after initialize; the step graph is kept.
+ * `type` must equal the row's stored type (a guard against a stale index). AA_ERR_ARG for a mesh
+ * row, a type mismatch, an index out of range, null or non-finite parameters. */
+int aa_elastic_set_obstacle(aa_elastic h, int index, int type, const double* params);
 /* Solver::set_collisions(inds, points) (admm_anderson_hard_zxu/src/Solver.cpp:318-344): one
  * Collision energy term (CollisionEnergyTerm.hpp:41-117: identity reduction, weight
  * sqrt(2 k(soft rubber)), prox = closest obstacle surface point when inside one) per listed node,
@@ -351,7 +380,11 @@ int aa_geom_set_comm(aa_geom h, aa_comm c);
  *     SLIDE_FLOOR normal is taken as given}, a row {AA_OBS_MESH, m} naming mesh m of the n_meshes
  *     meshes given concatenated (mesh m: vertices mesh_vert_ptr[m]..mesh_vert_ptr[m+1] of
  *     mesh_verts3, triangles mesh_tri_ptr[m]..mesh_tri_ptr[m+1] of mesh_tris3 with indices local
- *     to the mesh) */
+ *     to the mesh)
+ *   aa_test_mesh_sdf_posed / aa_test_collision_prox_posed: the same with kinematic poses
+ *     (aa_elastic_set_mesh_obstacle_pose; validated alike): pose12 for the one mesh, mesh_poses =
+ *     12 doubles per mesh (twelve NaNs: that mesh unposed); NULL = unposed. Queries and the reported closest point are in the
+ *     world frame, dx is the obstacle-frame distance. */
 int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double* in, int n, double* out, int* iters);
 int aa_test_cod_solve(aa_ctx ctx, int k, const double* M, const double* b, double* theta);
 int aa_test_geom_project(aa_ctx ctx, int type, int k, const double* prm2, const double* in, int n, double* out);
@@ -360,6 +393,11 @@ int aa_test_mesh_sdf(aa_ctx ctx, const double* verts3, int n_verts, const int* t
 int aa_test_collision_prox(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
                            const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr, int n_meshes,
                            const double* q3, int n, double* out3);
+int aa_test_mesh_sdf_posed(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
+                           const double* pose12, const double* q3, int n, double* closest3, double* dx, int* tri);
+int aa_test_collision_prox_posed(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
+                                 const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr, int n_meshes,
+                                 const double* mesh_poses, const double* q3, int n, double* out3);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@
 //   solver.ext_forces.push_back(std::make_shared<admm::WindForce>(faces));                    // wind
 //   solver.initialize(settings);                       // Solver::initialize (returns bool)
 //   solver.step();                                     // Solver::step; solver.m_x / m_v updated
+//   solver.set_obstacle_pose(mesh, R, t); solver.update_obstacle(floor);   // kinematic obstacles, between steps
 //
 // Energy terms are descriptors of the built-in element kinds (batched SoA on the device);
 // user-defined EnergyTerm subclasses with arbitrary prox() are not supported (no host
@@ -164,6 +165,7 @@ class PassiveMesh : public PassiveCollision {
 public:
     std::vector<double> verts;   // 3 per vertex
     std::vector<int> tris;       // 3 per triangle
+    int mesh_id = -1;            // its number in the solver it was added to (Solver::set_obstacle_pose)
     static PassiveMesh from_surface(const double* verts3, int n_verts, const int* tris3, int n_tris) {
         PassiveMesh m;
         m.verts.assign(verts3, verts3 + 3 * (size_t)n_verts);
@@ -285,10 +287,29 @@ public:
 
     // Solver::add_obstacle (Solver.cpp:346-348): takes effect at once, also between steps
     void add_obstacle(std::shared_ptr<PassiveCollision> obj) {
-        if (const PassiveMesh* m = dynamic_cast<const PassiveMesh*>(obj.get()))
-            check(aa_elastic_add_mesh_obstacle(h_, m->verts.data(), (int)m->verts.size() / 3, m->tris.data(), (int)m->tris.size() / 3, nullptr));
+        if (PassiveMesh* m = dynamic_cast<PassiveMesh*>(obj.get()))
+            check(aa_elastic_add_mesh_obstacle(h_, m->verts.data(), (int)m->verts.size() / 3, m->tris.data(), (int)m->tris.size() / 3, &m->mesh_id));
         else
             check(aa_elastic_add_obstacle(h_, obj->type, obj->params));
+        obstacles_.push_back(obj);   // its row in the insertion order
+    }
+    // Kinematic obstacles (no reference counterpart; aa_admm.h, aa_elastic_set_mesh_obstacle_pose):
+    // the mesh as added, turned by R (row-major 3x3, a rotation) and moved by t, for every later
+    // step until changed -- a paddle, a drum, a rising floor. R == nullptr: back to unposed.
+    void set_obstacle_pose(const std::shared_ptr<PassiveMesh>& mesh, const double R[9], const double t[3]) {
+        if (!mesh || mesh->mesh_id < 0 || row_of(mesh.get()) < 0) throw std::runtime_error("set_obstacle_pose: the mesh was not added to this solver");
+        if (!R) { check(aa_elastic_set_mesh_obstacle_pose(h_, mesh->mesh_id, nullptr)); return; }
+        double p[12];
+        for (int i = 0; i < 9; ++i) p[i] = R[i];
+        for (int i = 0; i < 3; ++i) p[9 + i] = t ? t[i] : 0.0;
+        check(aa_elastic_set_mesh_obstacle_pose(h_, mesh->mesh_id, p));
+    }
+    // ... and the analytic shapes: change obj->params, then call this to re-send them to the row
+    // the obstacle was added as
+    void update_obstacle(std::shared_ptr<PassiveCollision> obj) {
+        const int row = row_of(obj.get());
+        if (row < 0) throw std::runtime_error("update_obstacle: the obstacle was not added to this solver");
+        check(aa_elastic_set_obstacle(h_, row, obj->type, obj->params));
     }
     // Solver::set_collisions (Solver.cpp:318-344): the points are not used by the prox
     // Before the first initialize() the device solver has no nodes yet (see below): the list is
@@ -409,6 +430,12 @@ private:
     VecX x_seen_, v_seen_;
     std::vector<int> pins_, collisions_;
     std::vector<double> pin_pts_;
+    std::vector<std::shared_ptr<PassiveCollision>> obstacles_;   // by row of the insertion order
+    int row_of(const PassiveCollision* o) const {
+        for (size_t k = 0; k < obstacles_.size(); ++k)
+            if (obstacles_[k].get() == o) return (int)k;
+        return -1;
+    }
 };
 
 }  // namespace admm

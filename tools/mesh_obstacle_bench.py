@@ -9,9 +9,14 @@ differences between forms are the collision kernel's), the step time, and -- for
 share of collision nodes inside the mesh's root box at the end of each step, i.e. the share of
 lanes that pass the cull and walk the BVH.
 
+--posed measures the kinematic obstacle instead: the icosphere as above against the same icosphere
+given in a frame turned by a constant non-trivial pose's inverse and posed back
+(Solver.set_mesh_obstacle_pose), i.e. the same world surface through the posed path.
+
 Prints one JSON line; --out writes it to a file.
 
     python tools/mesh_obstacle_bench.py --out profiles/mesh_obstacle.json
+    python tools/mesh_obstacle_bench.py --posed --out profiles/kinematic_obstacle.json
 """
 import argparse
 import importlib
@@ -53,8 +58,17 @@ def icosphere(center, radius, level):
     return np.asarray(center, float) + radius * np.array(V), np.array(F, np.int32)
 
 
-def measure(ctx, sc, iters, steps, mesh=None):
+def rotation(axis, angle):
+    a = np.asarray(axis, float) / np.linalg.norm(axis)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
+
+
+def measure(ctx, sc, iters, steps, mesh=None, pose=None):
+    """mesh: the obstacle's world-frame surface (for the root-box share); pose: set on mesh 0."""
     s = capi.solver_from_scene(ctx, sc)
+    if pose is not None:
+        s.set_mesh_obstacle_pose(0, *pose)
     s.initialize(capi.settings_from_scene(sc))
     share, step_ms = [], []
     for _ in range(steps):
@@ -83,6 +97,7 @@ def main():
     ap.add_argument("--iters", type=int, default=60, help="iterations per bench_iterations call")
     ap.add_argument("--steps", type=int, default=18)
     ap.add_argument("--level", type=int, default=4, help="icosphere subdivisions (4: 5 120 triangles)")
+    ap.add_argument("--posed", action="store_true", help="the posed leg: icosphere unposed against a constant pose")
     ap.add_argument("--out")
     a = ap.parse_args()
     d = np.load(os.path.join(REPO, "tests", "golden", "mesh_horse759.npz"))
@@ -94,15 +109,23 @@ def main():
     ctx = capi.Context(0)
     res = {"scene": "obstacle_course(horse759)", "collision_nodes": int(len(base.collision_idx)),
            "library": os.path.basename(capi.LIB_PATH), "bench_iters": a.iters, "forms": {}}
-    forms = {"analytic_sphere": (base.obstacles, None), "no_sphere": (rest, None), "icosphere": (rest, mesh)}
-    for name, (obs, m) in forms.items():
+    forms = {"analytic_sphere": (base.obstacles, None, None), "no_sphere": (rest, None, None), "icosphere": (rest, mesh, None)}
+    if a.posed:
+        R, t = rotation((1.0, 2.0, 3.0), 0.7), np.array([0.3, -1.25, 2.0])
+        res["pose"] = {"axis": [1, 2, 3], "angle_rad": 0.7, "t": t.tolist()}
+        forms = {"icosphere": (rest, mesh, None), "icosphere_posed": (rest, mesh, (R, t))}
+    for name, (obs, m, pose) in forms.items():
         sc = S.obstacle_course(d["verts"], d["tets"], n_steps=a.steps)
         sc.obstacles = list(obs)
-        sc.mesh_obstacles = [m] if m is not None else []
-        res["forms"][name] = measure(ctx, sc, a.iters, a.steps, m)
+        if m is not None:   # posed: the surface given as R^T (v - t), so that the pose puts it back
+            sc.mesh_obstacles = [m if pose is None else ((m[0] - pose[1]) @ pose[0], m[1])]
+        res["forms"][name] = measure(ctx, sc, a.iters, a.steps, m, pose)
     f = res["forms"]
     med = lambda n: float(np.median(f[n]["local_z_us_per_pass"]))
-    res["icosphere_minus_analytic_sphere_us_per_pass"] = round(med("icosphere") - med("analytic_sphere"), 2)
+    if a.posed:
+        res["posed_minus_unposed_us_per_pass"] = round(med("icosphere_posed") - med("icosphere"), 2)
+    else:
+        res["icosphere_minus_analytic_sphere_us_per_pass"] = round(med("icosphere") - med("analytic_sphere"), 2)
     line = json.dumps(res)
     print(line)
     if a.out:
