@@ -36,7 +36,7 @@ EXPORTS = [
     "aa_geom_add_closeness", "aa_geom_add_laplacians", "aa_geom_add_closenesses", "aa_geom_setup", "aa_geom_solve", "aa_geom_set_stop", "aa_geom_get_solution", "aa_geom_get_history",
     "aa_geom_runtime_info", "aa_geom_closest_points", "aa_geom_bench_iterations", "aa_geom_kernel_stats",
     "aa_test_prox", "aa_test_cod_solve", "aa_test_geom_project", "aa_test_mesh_sdf", "aa_test_collision_prox",
-    "aa_test_mesh_sdf_posed", "aa_test_collision_prox_posed",
+    "aa_test_mesh_sdf_posed", "aa_test_collision_prox_posed", "aa_test_direct_solve",
 ]
 
 # Geometry constraint types (Geometry/Constraint.h) and SPD solver types (SolverCommon.h)
@@ -874,3 +874,69 @@ def hook_collision_prox(ctx: Context, obstacles, meshes, Q, poses=None):
     _chk(lib().aa_test_collision_prox(ctx.h, _dp(rows), C.c_int(len(obstacles)), _dp(vv), _ip(vptr), _ip(ff), _ip(fptr),
                                       C.c_int(len(meshes)), _dp(q), C.c_int(q.shape[0]), _dp(out)))
     return out
+
+
+# script entries of aa_test_direct_solve (include/aa_admm.h)
+(AA_SOLVE_B0, AA_SOLVE_B1, AA_SOLVE_BOTH, AA_SOLVE_GATED_SKIP_B0, AA_SOLVE_GATED_SKIP_B1, AA_SOLVE_GATED_TAKE_B0,
+ AA_SOLVE_GATED_TAKE_B1, AA_SOLVE_DONE_B0, AA_SOLVE_DONE_B1) = range(9)
+SOLVE_SENTINEL = -1.2345678901234567e+123   # what the output buffers hold before every script entry
+
+# DirectSolver::PlanSummary (csrc/direct_solve.hpp), field by field
+SOLVE_PLAN_FIELDS = (
+    "supernodes", "levels", "fused_subtrees", "fused_supernodes", "sub_u", "sub_x",
+    "fwd_tasks", "bwd_tasks", "fwd_tiles", "bwd_tiles", "fwd_tile_w", "bwd_tile_w",
+    "fwd_streams", "bwd_streams", "stream_all", "stream_gated", "branches", "packed", "nt", "nt_rows",
+    "row_p_min", "row_p_max", "row_R_min", "row_R_max", "tile_p_min", "tile_p_max", "tile_R_min", "tile_R_max",
+    "fwd_row_nodes", "fwd_tile_nodes", "bwd_row_nodes", "bwd_tile_nodes", "fwd_row_bwd_tile_nodes",
+    "fwd_tile_bwd_row_nodes", "multi_block_fwd_nodes", "odd_p_nodes", "sub_block", "wave_p", "wave_r", "max_sets",
+)
+
+
+class DirectSolveResult:
+    """x[k] = (first, second) output buffer of script entry k, each (n, 3) in the caller's ordering
+    (SOLVE_SENTINEL where the entry wrote nothing); x_host = factor_solve_host of (b0, b1) with the
+    same factor; plan = the PlanSummary as a dict; height / depth = per node, of its supernode."""
+
+    def __init__(self, x, x_host, plan, height, depth):
+        self.x, self.x_host, self.plan, self.height, self.depth = x, x_host, plan, height, depth
+
+
+def test_direct_solve(ctx: Context, A, xyz, b0, b1=None, script=(AA_SOLVE_B0,), tree=None, leaf_size=8, top_rows=0,
+                      wave_p=192, wave_r=384, max_sets=1, wide=False, default_branches=1, device_factor=False):
+    """aa_test_direct_solve: the GPU triangular solves alone on the SPD matrix A (scipy CSR, full
+    symmetric pattern with the diagonal stored). tree = (beg, end, parent): an explicit supernode
+    tree in postorder with the identity permutation; None: the library's nested dissection with
+    leaf_size / top_rows. The AA_SOLVE_* / AA_SUB_* / AA_FACTOR_NT* knobs are read from the
+    environment on every call."""
+    A = A.tocsr()
+    A.sort_indices()
+    n = A.shape[0]
+    ptr = np.ascontiguousarray(A.indptr, np.int32)
+    col = np.ascontiguousarray(A.indices, np.int32)
+    val = np.ascontiguousarray(A.data, np.float64)
+    xyz = np.ascontiguousarray(xyz, np.float64).reshape(n, 3)
+    b0 = np.ascontiguousarray(b0, np.float64).reshape(n, 3)
+    if b1 is not None:
+        b1 = np.ascontiguousarray(b1, np.float64).reshape(n, 3)
+    sc = np.ascontiguousarray(script, np.int32).reshape(-1)
+    if tree is not None:
+        tb, te, tp = (np.ascontiguousarray(a, np.int32) for a in tree)
+        nt = len(tb)
+    else:
+        tb = te = tp = np.zeros(1, np.int32)
+        nt = 0
+    x = np.zeros((max(len(sc), 1), 2, n, 3))
+    xh = np.zeros((2, n, 3))
+    info = np.zeros((n, 2), np.int32)
+    plan = np.zeros(len(SOLVE_PLAN_FIELDS), np.int32)
+    cnt = C.c_int()
+    _chk(lib().aa_test_direct_solve(
+        ctx.h, C.c_int(n), _dp(xyz), _ip(ptr), _ip(col), _dp(val), C.c_int(nt), _ip(tb), _ip(te), _ip(tp),
+        C.c_int(leaf_size), C.c_int(top_rows), C.c_int(wave_p), C.c_int(wave_r), C.c_int(max_sets), C.c_int(int(wide)),
+        C.c_int(default_branches), C.c_int(int(device_factor)), _dp(b0), _dp(b1) if b1 is not None else None,
+        C.c_int(len(sc)), _ip(sc), C.c_double(SOLVE_SENTINEL), _dp(x), _dp(xh), _ip(info), _ip(plan),
+        C.c_int(len(plan)), C.byref(cnt)))
+    if cnt.value != len(SOLVE_PLAN_FIELDS):
+        raise RuntimeError(f"PlanSummary has {cnt.value} fields, the binding names {len(SOLVE_PLAN_FIELDS)}")
+    return DirectSolveResult([(x[k, 0], x[k, 1]) for k in range(len(sc))], (xh[0], xh[1] if b1 is not None else None),
+                             dict(zip(SOLVE_PLAN_FIELDS, (int(v) for v in plan))), info[:, 0].copy(), info[:, 1].copy())

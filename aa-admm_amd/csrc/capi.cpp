@@ -654,6 +654,135 @@ extern "C" int aa_test_collision_prox_posed(aa_ctx ctx, const double* obs_rows, 
     });
 }
 
+extern "C" int aa_test_direct_solve(aa_ctx ctx, int n, const double* xyz3, const int* ptr, const int* col,
+                                    const double* val, int n_tree, const int* tree_beg, const int* tree_end,
+                                    const int* tree_parent, int leaf_size, int top_rows, int wave_p, int wave_r,
+                                    int max_sets, int wide, int default_branches, int device_factor, const double* b0,
+                                    const double* b1, int n_script, const int* script, double sentinel, double* x_out,
+                                    double* x_host, int* row_info, int* plan, int plan_cap, int* plan_count) {
+    return with_device_arrays(ctx, [&](hipStream_t s) {
+        NEED(n >= 1 && xyz3 && ptr && col && val && b0 && x_out && x_host, "aa_test_direct_solve: null argument");
+        NEED(n_tree >= 0 && (n_tree == 0 || (tree_beg && tree_end && tree_parent)), "aa_test_direct_solve: bad tree");
+        NEED(n_tree > 0 || leaf_size >= 1, "aa_test_direct_solve: leaf_size must be positive");
+        NEED((max_sets == 1 || max_sets == 2) && wave_p >= 0 && wave_r >= 0 && n_script >= 0 && (n_script == 0 || script),
+             "aa_test_direct_solve: bad argument");
+        NEED(ptr[0] == 0, "aa_test_direct_solve: bad CSR");
+        for (int i = 0; i < n; ++i) {
+            NEED(ptr[i + 1] >= ptr[i], "aa_test_direct_solve: bad CSR");
+            bool diag = false;
+            for (int k = ptr[i]; k < ptr[i + 1]; ++k) {
+                NEED(col[k] >= 0 && col[k] < n && (k == ptr[i] || col[k] > col[k - 1]), "aa_test_direct_solve: CSR columns must be sorted and in range");
+                diag = diag || col[k] == i;
+            }
+            NEED(diag, "aa_test_direct_solve: every diagonal entry must be stored");
+        }
+        for (int k = 0; k < n_script; ++k) {
+            const int op = script[k];
+            NEED(op >= AA_SOLVE_B0 && op <= AA_SOLVE_DONE_B1, "aa_test_direct_solve: unknown script entry");
+            const bool uses_b1 = op == AA_SOLVE_B1 || op == AA_SOLVE_BOTH || op == AA_SOLVE_GATED_SKIP_B1 ||
+                                 op == AA_SOLVE_GATED_TAKE_B1 || op == AA_SOLVE_DONE_B1;
+            NEED(!uses_b1 || b1, "aa_test_direct_solve: a script entry names b1, which was not given");
+            NEED(op != AA_SOLVE_BOTH || max_sets == 2, "aa_test_direct_solve: solve2 needs max_sets = 2");
+        }
+        // the tree and the matrix in its ordering
+        aa::NdTree tree;
+        if (n_tree > 0) {
+            tree = aa::explicit_tree(n, std::vector<int>(tree_beg, tree_beg + n_tree), std::vector<int>(tree_end, tree_end + n_tree),
+                                     std::vector<int>(tree_parent, tree_parent + n_tree));
+        } else {
+            std::vector<int> aptr(n + 1, 0), aj;
+            for (int i = 0; i < n; ++i) {
+                for (int k = ptr[i]; k < ptr[i + 1]; ++k) if (col[k] != i) aj.push_back(col[k]);
+                aptr[i + 1] = (int)aj.size();
+            }
+            tree = aa::nested_dissection(n, xyz3, aptr, aj, leaf_size, top_rows);
+        }
+        NEED((int)tree.perm.size() == n, "aa_test_direct_solve: the ordering lost nodes");
+        std::vector<int> inv(n);
+        for (int q = 0; q < n; ++q) inv[tree.perm[q]] = q;
+        aa::CsrMatrix A;
+        A.n = n;
+        A.ptr.assign(n + 1, 0);
+        A.col.reserve(ptr[n]);
+        A.val.reserve(ptr[n]);
+        std::vector<std::pair<int, double>> r;
+        for (int q = 0; q < n; ++q) {
+            const int i = tree.perm[q];
+            r.clear();
+            for (int k = ptr[i]; k < ptr[i + 1]; ++k) r.push_back({inv[col[k]], val[k]});
+            std::sort(r.begin(), r.end());
+            for (const auto& e : r) { A.col.push_back(e.first); A.val.push_back(e.second); }
+            A.ptr[q + 1] = (int)A.col.size();
+        }
+        aa::check_tree_covers(A, tree);
+        aa::SupernodalFactor F = device_factor ? aa::factor_on_device(A, tree, s) : aa::multifrontal_cholesky(A, tree);
+        // host yardstick with the same factor
+        const int nrhs = b1 ? 2 : 1;
+        std::vector<double> hb(3 * (size_t)n), bperm[2];
+        for (int k = 0; k < nrhs; ++k) {
+            const double* b = k ? b1 : b0;
+            bperm[k].resize(3 * (size_t)n);
+            for (int q = 0; q < n; ++q) for (int c = 0; c < 3; ++c) bperm[k][3 * (size_t)q + c] = b[3 * (size_t)tree.perm[q] + c];
+            hb = bperm[k];
+            aa::factor_solve_host(F, hb);
+            for (int q = 0; q < n; ++q)
+                for (int c = 0; c < 3; ++c) x_host[3 * ((size_t)k * n + tree.perm[q]) + c] = hb[3 * (size_t)q + c];
+        }
+        if (!b1) std::fill(x_host + 3 * (size_t)n, x_host + 6 * (size_t)n, sentinel);
+        if (row_info) {
+            std::vector<int> depth(F.n_nodes, 0);
+            for (int sn = F.n_nodes - 1; sn >= 0; --sn) depth[sn] = F.parent[sn] >= 0 ? depth[F.parent[sn]] + 1 : 0;
+            for (int sn = 0; sn < F.n_nodes; ++sn)
+                for (int q = F.beg[sn]; q < F.end[sn]; ++q) { row_info[2 * tree.perm[q]] = F.height[sn]; row_info[2 * tree.perm[q] + 1] = depth[sn]; }
+        }
+        // the device solver, built once, then the script
+        aa::DirectSolver solver;
+        solver.default_branches = default_branches;
+        solver.build(F, s, nullptr, -1, -1, nullptr, max_sets, wide != 0, wave_p, wave_r);
+        const aa::DirectSolver::PlanSummary P = solver.plan_summary();
+        static_assert(sizeof(P) % sizeof(int) == 0, "PlanSummary is ints only");
+        const int np = (int)(sizeof(P) / sizeof(int));
+        if (plan_count) *plan_count = np;
+        if (plan) std::memcpy(plan, &P, sizeof(int) * std::min(np, std::max(plan_cap, 0)));
+        aa::DevBuf<double> db[2], dx[2];
+        for (int k = 0; k < 2; ++k) {
+            dx[k].alloc(3 * (size_t)n);
+            if (k < nrhs) db[k].upload(bperm[k], s);
+        }
+        aa::DevBuf<aa::Ctrl> dctrl(1);
+        const std::vector<double> fill(3 * (size_t)n, sentinel);
+        std::vector<double> hx(3 * (size_t)n);
+        for (int k = 0; k < n_script; ++k) {
+            const int op = script[k];
+            for (int o = 0; o < 2; ++o) AA_HIP(hipMemcpyAsync(dx[o].p, fill.data(), sizeof(double) * fill.size(), hipMemcpyHostToDevice, s));
+            aa::Ctrl hc;
+            std::memset(&hc, 0, sizeof(hc));
+            int gate = 0, rhs = 0;
+            switch (op) {
+                case AA_SOLVE_B0: break;
+                case AA_SOLVE_B1: rhs = 1; break;
+                case AA_SOLVE_BOTH: break;
+                case AA_SOLVE_GATED_SKIP_B0: gate = 1; break;
+                case AA_SOLVE_GATED_SKIP_B1: gate = 1; rhs = 1; break;
+                case AA_SOLVE_GATED_TAKE_B0: gate = 1; hc.reject = 1; break;
+                case AA_SOLVE_GATED_TAKE_B1: gate = 1; hc.reject = 1; rhs = 1; break;
+                case AA_SOLVE_DONE_B0: hc.done = 1; break;
+                default: hc.done = 1; rhs = 1; break;
+            }
+            AA_HIP(hipMemcpyAsync(dctrl.p, &hc, sizeof(hc), hipMemcpyHostToDevice, s));
+            AA_HIP(hipStreamSynchronize(s));   // (hc and fill are pageable host memory)
+            if (op == AA_SOLVE_BOTH) solver.solve2(db[0].p, dx[0].p, db[1].p, dx[1].p, dctrl.p, 0, s);
+            else solver.solve(db[rhs].p, dx[0].p, dctrl.p, gate, s);
+            AA_HIP(hipStreamSynchronize(s));
+            for (int o = 0; o < 2; ++o) {
+                AA_HIP(hipMemcpy(hx.data(), dx[o].p, sizeof(double) * hx.size(), hipMemcpyDeviceToHost));
+                double* out = x_out + 3 * (size_t)n * (2 * (size_t)k + o);
+                for (int q = 0; q < n; ++q) for (int c = 0; c < 3; ++c) out[3 * (size_t)tree.perm[q] + c] = hx[3 * (size_t)q + c];
+            }
+        }
+    });
+}
+
 extern "C" int aa_test_cod_solve(aa_ctx ctx, int k, const double* M, const double* b, double* theta) {
     return with_device_arrays(ctx, [&](hipStream_t s) {
         NEED(M && b && theta && k >= 1 && k <= aa::kMaxM, "aa_test_cod_solve: bad argument");

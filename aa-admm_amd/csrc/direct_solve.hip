@@ -1373,6 +1373,8 @@ void DirectSolver::build(const SupernodalFactor& F, hipStream_t s, const std::ve
         n_sub_ = (int)strees.size();
         plan_sub_lds(F, kids, p, nb, beg, uoff, bnd_off, ell_w, ell_off, ell, bnd, fidx, bidx, sub_all, strees, snodes, KS,
                      stats, s);
+        plan_ = PlanSummary{};
+        for (const SubTree& T : strees) { plan_.sub_u += (T.flags & kSubU) != 0; plan_.sub_x += (T.flags & kSubX) != 0; }
         // ---- branches (AA_SOLVE_BRANCHES, see direct_solve.hpp): disjoint subtrees of the tree
         // solved on parallel streams, the supernodes above them ("top") after the join
         plan_branches(F, inc, fused, kids, p, nb, stats);
@@ -1929,6 +1931,36 @@ void DirectSolver::build(const SupernodalFactor& F, hipStream_t s, const std::ve
         nt_rows_ = er ? er[0] == '1' : (nt_ && 2.0 * 8.0 * (dense + offd) < kNtRowsMaxBytes);
     }
     bytes2_ = 2.0 * 8.0 * (dense + offd) + 2.0 * (4.0 * 24.0 * piv + 3.0 * 24.0 * bsum);
+    {   // the plan in numbers (plan_summary())
+        PlanSummary& S = plan_;
+        S.supernodes = nn_; S.levels = (int)levels_.size();
+        S.fused_subtrees = n_sub_;
+        for (int sn = 0; sn < nn_; ++sn) S.fused_supernodes += fused[sn] != 0;
+        for (const Level& L : levels_) {
+            S.fwd_tasks += L.fwd_count; S.bwd_tasks += L.bwd_count;
+            S.fwd_tiles += L.ft_count; S.bwd_tiles += L.bt_count;
+            if (L.ft_count) S.fwd_tile_w |= L.ftw;
+            if (L.bt_count) S.bwd_tile_w |= L.btw;
+        }
+        S.fwd_streams = (int)fstreams_.size(); S.bwd_streams = (int)bstreams_.size();
+        S.stream_all = stream_; S.stream_gated = stream_gated_;
+        S.branches = nbr_;
+        S.packed = packed_; S.nt = nt_; S.nt_rows = nt_rows_;
+        auto span = [](int& lo, int& hi, int v, bool first) { lo = first ? v : std::min(lo, v); hi = first ? v : std::max(hi, v); };
+        int nrow = 0, ntile = 0;
+        for (int sn = 0; sn < nn_; ++sn) {
+            if (lev_of[sn] < 0) continue;
+            const int R = p[sn] + nb[sn];
+            const bool frow = p[sn] <= wave_p_, brow = R <= wave_r_;
+            S.fwd_row_nodes += frow; S.fwd_tile_nodes += !frow; S.bwd_row_nodes += brow; S.bwd_tile_nodes += !brow;
+            S.fwd_row_bwd_tile_nodes += frow && !brow; S.fwd_tile_bwd_row_nodes += !frow && brow;
+            S.odd_p_nodes += p[sn] & 1;
+            if (frow && R > levels_[lev_of[sn]].fblock) ++S.multi_block_fwd_nodes;
+            if (frow || brow) { span(S.row_p_min, S.row_p_max, p[sn], nrow == 0); span(S.row_R_min, S.row_R_max, R, nrow == 0); ++nrow; }
+            if (!frow || !brow) { span(S.tile_p_min, S.tile_p_max, p[sn], ntile == 0); span(S.tile_R_min, S.tile_R_max, R, ntile == 0); ++ntile; }
+        }
+        S.sub_block = sub_block_; S.wave_p = wave_p_; S.wave_r = wave_r_; S.max_sets = max_sets_;
+    }
     AA_HIP(hipStreamSynchronize(s));
 }
 

@@ -67,6 +67,26 @@ public:
     double bytes_per_solve2() const { return bytes2_; }
     int kernels_per_solve() const { return kernels_; }
 
+    // What build() planned, for tests that must know which kernels a solve runs (capi.cpp
+    // aa_test_direct_solve). Row-task / tiled supernodes: the level-scheduled (not fused) ones
+    // whose forward or backward sweep runs as row tasks / split-K tiles (a supernode can be both).
+    struct PlanSummary {
+        int supernodes, levels;                       // all supernodes; level-scheduled heights
+        int fused_subtrees, fused_supernodes, sub_u, sub_x;   // subtrees with kSubU / kSubX
+        int fwd_tasks, bwd_tasks, fwd_tiles, bwd_tiles;
+        int fwd_tile_w, bwd_tile_w;                   // widths in use, or'ed (64 | 128 | 256); 0: no tiles
+        int fwd_streams, bwd_streams, stream_all, stream_gated;   // streamed runs; which solves take them
+        int branches;
+        int packed, nt, nt_rows;
+        int row_p_min, row_p_max, row_R_min, row_R_max;       // over row-task supernodes (0 when none)
+        int tile_p_min, tile_p_max, tile_R_min, tile_R_max;   // over tiled supernodes
+        int fwd_row_nodes, fwd_tile_nodes, bwd_row_nodes, bwd_tile_nodes;
+        int fwd_row_bwd_tile_nodes, fwd_tile_bwd_row_nodes;   // the two mixed classes
+        int multi_block_fwd_nodes, odd_p_nodes;       // row-task supernodes over several forward blocks; odd p
+        int sub_block, wave_p, wave_r, max_sets;
+    };
+    const PlanSummary& plan_summary() const { return plan_; }
+
     // One workgroup's share of a level: rows [r0, r0 + nr) of supernode `node` (forward) or
     // its columns (backward), a thread per row. The supernode's metadata rides along so a
     // workgroup needs one (scalar) load before its first product.
@@ -154,6 +174,7 @@ private:
     size_t nnz_L_ = 0;
     double bytes_ = 0, bytes2_ = 0;
     int max_sets_ = 1;
+    PlanSummary plan_{};
     template <int NR>
     void launch_ftiles(int w, int count, int first, const double* b0, const double* b1, int ext_off, const Ctrl* ctrl,
                        int gate_reject, hipStream_t s);

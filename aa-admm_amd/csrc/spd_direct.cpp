@@ -248,6 +248,47 @@ NdTree nested_dissection(int n, const double* xyz, const std::vector<int>& adj_p
     return t;
 }
 
+NdTree explicit_tree(int n, const std::vector<int>& beg, const std::vector<int>& end, const std::vector<int>& parent) {
+    const int nn = (int)beg.size();
+    if (n < 0 || nn < 1 || (int)end.size() != nn || (int)parent.size() != nn)
+        throw std::runtime_error("explicit_tree: beg, end and parent must have one entry per supernode");
+    NdTree t;
+    int c = 0;
+    for (int s = 0; s < nn; ++s) {
+        if (beg[s] != c || end[s] < beg[s]) throw std::runtime_error("explicit_tree: pivot ranges are not contiguous from 0");
+        c = end[s];
+        if (parent[s] != -1 && (parent[s] <= s || parent[s] >= nn)) throw std::runtime_error("explicit_tree: not a postorder");
+    }
+    if (c != n) throw std::runtime_error("explicit_tree: pivot ranges do not cover [0, n)");
+    t.perm.resize(n);
+    for (int i = 0; i < n; ++i) t.perm[i] = i;
+    t.beg = beg; t.end = end; t.parent = parent;
+    t.children.resize(nn);
+    for (int s = 0; s < nn; ++s) if (parent[s] >= 0) t.children[parent[s]].push_back(s);
+    t.part.assign(nn, 0);
+    t.n_parts = 1;
+    t.part_beg.assign(1, 0);
+    t.part_end.assign(1, n);
+    t.top_beg = 0;
+    return t;
+}
+
+void check_tree_covers(const CsrMatrix& A, const NdTree& tree) {
+    const int nn = (int)tree.beg.size();
+    std::vector<int> owner(A.n, -1);
+    for (int s = 0; s < nn; ++s) for (int j = tree.beg[s]; j < tree.end[s]; ++j) owner[j] = s;
+    for (int s = 0; s < nn; ++s)
+        for (int j = tree.beg[s]; j < tree.end[s]; ++j)
+            for (int k = A.ptr[j]; k < A.ptr[j + 1]; ++k) {
+                const int i = A.col[k];
+                if (i < 0 || i >= A.n) throw std::runtime_error("check_tree_covers: column index out of range");
+                if (i < tree.end[s]) continue;
+                int a = tree.parent[s];
+                while (a >= 0 && a != owner[i]) a = tree.parent[a];
+                if (a < 0) throw std::runtime_error("check_tree_covers: an entry couples a supernode to one that is not its ancestor");
+            }
+}
+
 // ------------------------------------------------------------------ multifrontal Cholesky
 namespace {
 

@@ -58,6 +58,16 @@ NdTree nested_dissection(int n, const double* xyz, const std::vector<int>& adj_p
                          int leaf_size, int top_rows = 0, int n_parts = 0, bool merge_top = true,
                          int part_top_rows = 0);
 
+// A caller-given supernode tree instead of a dissection (tests that need exact supernode shapes):
+// pivot ranges [beg[s], end[s]) in postorder covering [0, n), parent[s] > s or -1, identity
+// permutation. Throws std::runtime_error when the arrays are not such a tree.
+NdTree explicit_tree(int n, const std::vector<int>& beg, const std::vector<int>& end, const std::vector<int>& parent);
+
+// Throws std::runtime_error unless every entry of A (in the tree's ordering) below a supernode's
+// diagonal block lies in one of the supernode's ancestors -- what multifrontal_cholesky assumes of
+// its tree (a dissection guarantees it; an explicit tree has to be checked).
+void check_tree_covers(const CsrMatrix& A, const NdTree& tree);
+
 struct SupernodalFactor {
     int n = 0;
     int n_nodes = 0;

@@ -398,6 +398,35 @@ int aa_test_mesh_sdf_posed(aa_ctx ctx, const double* verts3, int n_verts, const 
 int aa_test_collision_prox_posed(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
                                  const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr, int n_meshes,
                                  const double* mesh_poses, const double* q3, int n, double* out3);
+/* The global step's sparse triangular solve alone (DirectSolver, csrc/direct_solve.hpp), on a
+ * caller-given SPD matrix: full-pattern symmetric CSR (ptr, col, val; sorted columns, every
+ * diagonal stored) of order n in the caller's ordering, node coordinates xyz3.
+ *   tree: n_tree = 0 runs nested_dissection(leaf_size, top_rows); n_tree > 0 gives the supernode
+ *     tree itself -- pivot ranges [tree_beg[s], tree_end[s]) in postorder covering [0, n), parent
+ *     (-1 = root) -- with the identity permutation; every off-diagonal entry of a supernode's
+ *     columns must lie in the supernode or in one of its ancestors.
+ *   build: wave_p, wave_r, max_sets (1 | 2), wide, default_branches as DirectSolver::build takes
+ *     them; the AA_SOLVE_* / AA_SUB_* / AA_FACTOR_NT* knobs are read from the environment by
+ *     build() as always (a fresh solver is built on every call).
+ *   device_factor: 0 = multifrontal_cholesky on the host, 1 = factor_on_device (AA_DENSE_MIN_FRONT).
+ *   script: n_script entries run in order on the one solver: AA_SOLVE_B0 / _B1 = solve(b),
+ *     AA_SOLVE_BOTH = solve2(b0, b1), AA_SOLVE_GATED_SKIP_* = gated solve with ctrl->reject = 0
+ *     (skipped), AA_SOLVE_GATED_TAKE_* = gated with reject = 1 (taken), AA_SOLVE_DONE_* = solve
+ *     with ctrl->done = 1 (skipped). b1 may be NULL when no entry names it. Both output buffers
+ *     are filled with `sentinel` before every entry.
+ *   x_out: n_script x 2 x n x 3, per entry the two output buffers (the second is written by
+ *     AA_SOLVE_BOTH only) un-permuted to the caller's ordering; x_host: 2 x n x 3,
+ *     factor_solve_host of b0 and b1 with the same factor; row_info: n x 2 (may be NULL), per node
+ *     the height and the depth (root = 0) of the supernode that owns it; plan: the
+ *     DirectSolver::PlanSummary as ints (plan_cap of them at most; *plan_count = how many there are). */
+enum { AA_SOLVE_B0 = 0, AA_SOLVE_B1 = 1, AA_SOLVE_BOTH = 2, AA_SOLVE_GATED_SKIP_B0 = 3, AA_SOLVE_GATED_SKIP_B1 = 4,
+       AA_SOLVE_GATED_TAKE_B0 = 5, AA_SOLVE_GATED_TAKE_B1 = 6, AA_SOLVE_DONE_B0 = 7, AA_SOLVE_DONE_B1 = 8 };
+int aa_test_direct_solve(aa_ctx ctx, int n, const double* xyz3, const int* ptr, const int* col, const double* val,
+                         int n_tree, const int* tree_beg, const int* tree_end, const int* tree_parent, int leaf_size,
+                         int top_rows, int wave_p, int wave_r, int max_sets, int wide, int default_branches,
+                         int device_factor, const double* b0, const double* b1, int n_script, const int* script,
+                         double sentinel, double* x_out, double* x_host, int* row_info, int* plan, int plan_cap,
+                         int* plan_count);
 
 #ifdef __cplusplus
 }
