@@ -550,6 +550,11 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     // to default_u in the window and restored from it on a reject
     win_u_ = conc_;
     if (const char* e = std::getenv("AA_Z_WINDOW")) win_u_ = win_u_ && e[0] != '0';
+    // the combined-residual pass's residual folded into its local step (comb_finish_z);
+    // AA_COMB_FUSED=0: local step into cz_, then k_prim_z over it, and the Anderson mix in its
+    // window bucket's instantiation (k_aa_mix<8> for m <= 8) -- the path before the fold, for the A/B
+    comb_fused_ = true;
+    if (const char* e = std::getenv("AA_COMB_FUSED")) comb_fused_ = e[0] != '0';
     // Z variant + Anderson: the two-set layout whether pipelined or not (same sums, same bits)
     stamp("factor");
     // the sweeps as two parallel branches (DirectSolver::plan_branches): measured on C4 (one GPU,
@@ -717,7 +722,8 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     lq_ = make_local_queue(ctx_->device, lzq_.p);
     if (conc_) {
         // the concurrent pass writes no rhs slots, so it runs the fused refill without their loads
-        // (k_local_z_hqf<4, false>: 412 registers, room beside it for the Anderson kernels; the
+        // (k_local_z_hqf<4, false>: 412 registers, 426 in the residual form comb_finish_z launches --
+        // room beside it for the Anderson kernels of up to 80; the
         // slot-writing form's 452 leave none -- C4 with that on both passes: the main step 25 us
         // faster, the iteration 100 us slower). Same box, 8 steps: the plain refill in this pass
         // 457.7 / 459.8 it/s, the fused one 459.2 / 464.8
@@ -869,14 +875,6 @@ void ElasticSolver::local_z_all(const double* xfull, const double* u, double* z,
     if (timed) ev_end("local_z");
 }
 
-// the element prox of every group on stream st with control block c (no partials, no slots)
-void ElasticSolver::local_z_on(const double* xfull, const double* u, double* z, int mode, hipStream_t st, Ctrl* c,
-                               const LocalQueue* q) {
-    for (auto& g : groups_)
-        launch_local_z(g.d, xfull, u, z, nullptr, nf_, st_.variant, mode, c, nullptr, 0, st, use_queue_ ? q : nullptr,
-                       g.var, mesh_table(g.d));
-}
-
 void ElasticSolver::prologue() {
     upload_pins();
     const bool accel = st_.acceleration_type == 1;
@@ -971,7 +969,7 @@ void ElasticSolver::enqueue_iteration_ux(bool accel) {
                          hist_prim_.p, hist_comb_.p, hist_rej_.p);
         reduce_aa();
         launch_aa_solve(c, aag_, aa_blocks_, m, s());
-        launch_aa_mix(G, aa_cur_.p, Z_, aa_dF_.p, aa_dG_.p, c, G, m, s());
+        launch_aa_mix(G, aa_cur_.p, Z_, aa_dF_.p, aa_dG_.p, c, G, m, s(), comb_fused_);
         ev_end("aa");
     } else {
         launch_control(CTL_COMB_UX, c, ga_, gb_, nbg_, accel, hist_prim_.p, hist_comb_.p, hist_rej_.p, s());
@@ -1107,7 +1105,7 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
         }
         if (!instrument_) copy_defaults();
         launch_aa_solve(c, aag_, aa_blocks_, m, s());
-        launch_aa_mix(G, z_.p, Z_, aa_dF_.p, aa_dG_.p, c, out, m, s());   // in place (out == cur)
+        launch_aa_mix(G, z_.p, Z_, aa_dF_.p, aa_dG_.p, c, out, m, s(), comb_fused_);   // in place (out == cur)
         ev_end("aa");
         // combined residual "for drawing figures" (Solver.cpp:217-233): extra solve + update_z
         if (pipe) {   // its rhs now (the next iteration overwrites the slots); the rest next iteration
@@ -1136,17 +1134,29 @@ void ElasticSolver::enqueue_iteration_z(bool accel, int it) {
     launch_control(CTL_COMB_Z, c, ga_, gb_, nbg_, accel, hist_prim_.p, hist_comb_.p, hist_rej_.p, s());
 }
 
-// comb pass after its solve: z_c = update_z(x_c, curr_u) into cz_, dual = W (z_c - default_z),
+// comb pass after its solve: z_c = update_z(x_c, curr_u), dual = W (z_c - default_z),
 // prim = D x_c - W z_c - C, comb = |prim|^2 + |dual|^2 and the break test (Solver.cpp:224-246).
 // du / dz: curr_u and default_z of the iteration the pass belongs to (when pipelined, u_ already
 // holds the next iteration's u). On stream st with control block c and partials pa / pb: the
 // solver's own, or (concurrent pass) the side stream's copies, summed only there -- one GPU.
 void ElasticSolver::comb_finish_z(int op, hipStream_t st, Ctrl* c, double* pa, double* pb, const LocalQueue* q,
                                   const double* du, const double* dz) {
-    local_z_on(cxfull_.p, du, cz_.p, LZ_NORMAL, st, c, q);
+    // Per group: the queue's residual form (comb_fused_, AA_COMB_FUSED=0 turns it off) leaves two
+    // sums per element in the group's range of cz_ -- nothing else reads z_c -- and k_prim_sum
+    // forms k_prim_z's block partials from them; every other group (pins, linear tets, triangles,
+    // collisions, the plain or split queue, no queue) runs its local step into cz_ and k_prim_z
+    // over it. Either way the group's partials land in its own range of pa / pb, with the same bits.
+    const LocalQueue* lq = use_queue_ ? q : nullptr;
+    auto fused = [&](const DevGroup& g) { return comb_fused_ && local_z_res_ok(g.d, lq); };
+    for (auto& g : groups_) {
+        if (fused(g)) launch_local_z_res(g.d, cxfull_.p, du, dz, cz_.p, nf_, c, st, lq, g.var);
+        else launch_local_z(g.d, cxfull_.p, du, cz_.p, nullptr, nf_, st_.variant, LZ_NORMAL, c, nullptr, 0, st, lq, g.var,
+                            mesh_table(g.d));
+    }
     int off = 0;
     for (auto& g : groups_) {
-        launch_prim_z(g.d, cxfull_.p, cz_.p, dz, nf_, 0, c, pa, pb, off, st);
+        if (fused(g)) launch_prim_sum(g.d, cz_.p, c, pa, pb, off, st);
+        else launch_prim_z(g.d, cxfull_.p, cz_.p, dz, nf_, 0, c, pa, pb, off, st);
         off += blocks_for(g.d.count);
     }
     if (st == s()) {

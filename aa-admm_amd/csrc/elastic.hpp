@@ -212,6 +212,9 @@ private:
     // of u on a reject (the reject branch reads du_at(it - 1) where it lies); u_ is then unused
     bool win_u_ = false;
     double* u_at(int it) { return win_u_ ? du_at(it) : u_.p; }
+    // the combined-residual pass forms its two residual sums per element inside its local step
+    // (no z_c round trip through cz_); AA_COMB_FUSED=0: local step, then k_prim_z
+    bool comb_fused_ = true;
 
     // kernel-class event timing (bench only)
     bool instrument_ = false;
@@ -232,8 +235,6 @@ private:
     void fetch_results();
     int nb_elems() const { return red_blocks_; }
     void local_z_all(const double* xfull, const double* u, double* z, double* y, int mode, bool red);
-    void local_z_on(const double* xfull, const double* u, double* z, int mode, hipStream_t st, Ctrl* c,
-                    const LocalQueue* q);
 };
 
 }  // namespace aa

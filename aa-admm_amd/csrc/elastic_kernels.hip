@@ -209,6 +209,18 @@ __device__ __forceinline__ void load_u(const GroupDev& g, int e, const double* _
 template <class... V>
 constexpr bool kVar = sizeof...(V) != 0;
 __device__ __forceinline__ const GroupVar& var_of(const GroupVar& v) { return v; }
+// the head of the pack in the residual form of k_local_z_hqf (before an optional GroupVar):
+// default_z of the iteration the combined-residual pass belongs to
+struct ResArgs {
+    const double* zref;
+};
+template <class... V>
+constexpr bool kRes = false;
+template <class... V>
+constexpr bool kRes<ResArgs, V...> = true;
+__device__ __forceinline__ const GroupVar& var_of(const ResArgs&, const GroupVar& v) { return v; }
+__device__ __forceinline__ const ResArgs& res_of(const ResArgs& r) { return r; }
+__device__ __forceinline__ const ResArgs& res_of(const ResArgs& r, const GroupVar&) { return r; }
 // a lane's live (mu, lambda, k) in the work-queue kernels of a per-element group: the values of
 // the element the lane holds, set at the refill (a uniform group reads GroupDev's scalars)
 template <bool VAR>
@@ -435,14 +447,25 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hq(GroupDev g, const double*
 // combined-residual pass writes no slots and runs SLOTS = false: without the slot loads it holds
 // 412 registers, which do leave that room (ElasticSolver::initialize). C4 (same box, two A/B
 // pairs): local_z 433 / 435 -> 422 / 418 us.
+//
+// The residual form (a ResArgs at the head of the pack, SLOTS = false), for the combined-residual
+// pass, whose z_c has one reader: k_prim_z, which reduces it with default_z and F = P x_c to two
+// numbers per element. Here the lane that finishes an element forms them itself -- it keeps F from
+// the refill, its iterate x[] is z_c, and the finished element's default_z (zref) and w ride in the
+// refill's first load group -- with k_prim_z's statements, loop order and accumulators, and
+// writes (pa, pb) to z[zoff + e] / z[zoff + count + e] where the z store was: 16 B per element out
+// instead of 72 B out and 72 + 72 + 96 B back in. k_prim_sum turns them into k_prim_z's block
+// partials. 426 registers (432 allocated): with k_aa_mix<6>'s 73 (80) a SIMD's 512 are exactly
+// full. The forms without ResArgs compile to the code they had before it existed.
 template <int NV, bool SLOTS = true, class... V>
 __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double* __restrict__ xfull,
                                                         const double* __restrict__ u, double* __restrict__ z,
                                                         double* __restrict__ y, int nf, int mode, Ctrl* ctrl,
                                                         int* __restrict__ queue, int refill,
                                                         unsigned long long* __restrict__ stats, V... gvp) {
-    constexpr bool VAR = kVar<V...>;
+    constexpr bool RES = kRes<V...>, VAR = sizeof...(V) > (RES ? 1 : 0);
     static_assert(NV == 4, "the fused refill is for tets");
+    static_assert(!(RES && SLOTS), "the residual form writes no slots");
     if (mode != LZ_INIT && gated(ctrl, mode == LZ_REDO)) return;
     unsigned trips = 0, refills = 0;
     __shared__ unsigned hist[101];
@@ -455,6 +478,7 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double
     dev::HyperLbfgs L;
     [[maybe_unused]] LaneMat<VAR> M;
     double v[D], x[D];
+    [[maybe_unused]] double Fk[RES ? D : 1];   // RES: F = P x_c of the lane's element, kept from the refill
     double vol = 0;
     int e = 0, fail = 0;
     bool active = false, pending = false, exhausted = false;
@@ -481,6 +505,12 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double
                 load_u<D>(g, e, u, uo);
                 wo = g.w[e];
             }
+            [[maybe_unused]] double zr[RES ? D : 1];   // RES: the finished element's default_z and w
+            if constexpr (RES) {
+#pragma unroll
+                for (int i = 0; i < D; ++i) zr[i] = res_of(gvp...).zref[g.zoff + (size_t)i * n + e];
+                wo = g.w[e];
+            }
             b = __shfl(b, leader, 64);
             const int my = b + rank;
             const int en = min(my, g.count - 1);
@@ -488,8 +518,21 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double
 #pragma unroll
             for (int a = 0; a < NV; ++a) id[a] = g.idx[a * n + en];
             if (pending) {   // the finished element's outputs while the ids are in flight
+                if constexpr (RES) {   // k_prim_z's two sums of the element instead of its z
+                    double pa = 0, pb = 0;
 #pragma unroll
-                for (int i = 0; i < D; ++i) z[g.zoff + (size_t)i * n + e] = x[i];
+                    for (int i = 0; i < D; ++i) {
+                        const double r = wo * (Fk[i] - x[i]);
+                        pa += r * r;
+                        const double d = wo * (x[i] - zr[i]);
+                        pb += d * d;
+                    }
+                    z[g.zoff + e] = pa;
+                    z[g.zoff + n + e] = pb;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < D; ++i) z[g.zoff + (size_t)i * n + e] = x[i];
+                }
                 if (SLOTS && y) {
                     double Cp[D];
 #pragma unroll
@@ -534,6 +577,7 @@ __global__ __launch_bounds__(kBlock) void k_local_z_hqf(GroupDev g, const double
                     for (int i = 0; i < D; ++i) {
                         v[i] = F[i] + un[i] / wn;
                         x[i] = v[i];
+                        if constexpr (RES) Fk[i] = F[i];
                     }
                     vol = voln;
                     bool ok;
@@ -851,6 +895,24 @@ __global__ __launch_bounds__(kBlock) void k_prim_z(GroupDev g, const double* __r
     const double sa = block_sum(pa, sm);
     const double sb = block_sum(pb, sm);
     if (threadIdx.x == 0) { red_a[red_off + blockIdx.x] = sa; if (red_b) red_b[red_off + blockIdx.x] = sb; }
+}
+
+// k_prim_z's block partials from per-element sums (pe: pa at zoff + e, pb at zoff + count + e, as
+// k_local_z_hqf<4, false, ResArgs> leaves them): the same thread-to-element layout, block sum and
+// gate, so the partials have k_prim_z's bits
+__global__ __launch_bounds__(kBlock) void k_prim_sum(GroupDev g, const double* __restrict__ pe, Ctrl* ctrl,
+                                                     double* red_a, double* red_b, int red_off) {
+    if (gated(ctrl, 0)) return;
+    __shared__ double sm[kBlock / 64];
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    double pa = 0, pb = 0;
+    if (e < g.count) {
+        pa = pe[g.zoff + e];
+        pb = pe[g.zoff + (size_t)g.count + e];
+    }
+    const double sa = block_sum(pa, sm);
+    const double sb = block_sum(pb, sm);
+    if (threadIdx.x == 0) { red_a[red_off + blockIdx.x] = sa; red_b[red_off + blockIdx.x] = sb; }
 }
 
 template <int NV>
@@ -1823,6 +1885,30 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
     AA_CHECK_LAUNCH();
 }
 
+bool local_z_res_ok(const GroupDev& g, const LocalQueue* queue) {
+    return g.kind == 0 && g.mat != 0 && !g.pinned && queue && queue->counter && queue->fused && !queue->split;
+}
+
+void launch_local_z_res(const GroupDev& g, const double* xfull, const double* u, const double* zref, double* pe, int nf,
+                        Ctrl* ctrl, hipStream_t s, const LocalQueue* queue, const GroupVar& var) {
+    if (g.count == 0) return;
+    const dim3 grid(std::min(blocks_for(g.count), std::max(1, queue->resident)));
+    if (var)
+        hipLaunchKernelGGL((k_local_z_hqf<4, false, ResArgs, GroupVar>), grid, dim3(kBlock), 0, s, g, xfull, u, pe, nullptr,
+                           nf, (int)LZ_NORMAL, ctrl, queue->counter, queue->refill_lanes, queue->stats, ResArgs{zref}, var);
+    else
+        hipLaunchKernelGGL((k_local_z_hqf<4, false, ResArgs>), grid, dim3(kBlock), 0, s, g, xfull, u, pe, nullptr, nf,
+                           (int)LZ_NORMAL, ctrl, queue->counter, queue->refill, queue->stats, ResArgs{zref});
+    AA_CHECK_LAUNCH();
+}
+
+void launch_prim_sum(const GroupDev& g, const double* pe, Ctrl* ctrl, double* red_a, double* red_b, int red_off,
+                     hipStream_t s) {
+    if (g.count == 0) return;
+    hipLaunchKernelGGL(k_prim_sum, dim3(blocks_for(g.count)), dim3(kBlock), 0, s, g, pe, ctrl, red_a, red_b, red_off);
+    AA_CHECK_LAUNCH();
+}
+
 void launch_resid_update_u(const GroupDev& g, const double* xfull, const double* xlast, const double* z, double* u,
                            int nf, Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s) {
     if (g.count == 0) return;
@@ -2069,9 +2155,15 @@ void launch_aa_solve(Ctrl* ctrl, const double* red, int nblocks, int m, hipStrea
 }
 
 void launch_aa_mix(Seg2 G, double* cur, long long eff, double* dF, double* dG, Ctrl* ctrl, Seg2 out, int m,
-                   hipStream_t s) {
+                   hipStream_t s, bool narrow) {
     const long long dim = G.na + G.nb;
-    switch (mm_bucket(m)) {
+    // m <= 6 / 7 have instantiations of their own (73 / 79 registers against 85 at 8: beside the comb
+    // pass's residual form only 80 fit on a SIMD). The c < mk guards make the arithmetic that of
+    // the 8 bucket; k_aa_reduce / k_aa_solve keep the bucket, which sets their partial layout
+    // (narrow = false: the bucket's instantiation, for the A/B)
+    switch (narrow && m <= 6 ? 6 : (narrow && m == 7 ? 7 : mm_bucket(m))) {
+        case 6: hipLaunchKernelGGL(k_aa_mix<6>, dim3(grid_for(dim)), dim3(kBlock), 0, s, G, cur, eff, dF, dG, ctrl, out); break;
+        case 7: hipLaunchKernelGGL(k_aa_mix<7>, dim3(grid_for(dim)), dim3(kBlock), 0, s, G, cur, eff, dF, dG, ctrl, out); break;
         case 8: hipLaunchKernelGGL(k_aa_mix<8>, dim3(grid_for(dim)), dim3(kBlock), 0, s, G, cur, eff, dF, dG, ctrl, out); break;
         case 12: hipLaunchKernelGGL(k_aa_mix<12>, dim3(grid_for(dim)), dim3(kBlock), 0, s, G, cur, eff, dF, dG, ctrl, out); break;
         case 16: hipLaunchKernelGGL(k_aa_mix<16>, dim3(grid_for(dim)), dim3(kBlock), 0, s, G, cur, eff, dF, dG, ctrl, out); break;

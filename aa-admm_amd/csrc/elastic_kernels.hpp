@@ -113,6 +113,16 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
                     int variant, int mode, Ctrl* ctrl, double* red, int red_off, hipStream_t s,
                     const LocalQueue* queue = nullptr, const GroupVar& var = GroupVar(),
                     const MeshObsDev* meshes = nullptr);
+// The combined-residual pass's local step with its residual folded in (k_local_z_hqf<4, false, ResArgs>):
+// per element |w(P x - z_c)|^2 to pe[zoff + e] and |w(z_c - zref)|^2 to pe[zoff + count + e], with
+// k_prim_z's statements; z_c itself is not stored. local_z_res_ok: the groups that take it -- those
+// the fused-refill queue serves (hyperelastic tets without pins, AA_LQ_FUSED on, no AA_LQ_SPLIT).
+// launch_prim_sum: k_prim_z's block partials from pe (same layout, block sum and gate: same bits)
+bool local_z_res_ok(const GroupDev& g, const LocalQueue* queue);
+void launch_local_z_res(const GroupDev& g, const double* xfull, const double* u, const double* zref, double* pe, int nf,
+                        Ctrl* ctrl, hipStream_t s, const LocalQueue* queue, const GroupVar& var = GroupVar());
+void launch_prim_sum(const GroupDev& g, const double* pe, Ctrl* ctrl, double* red_a, double* red_b, int red_off,
+                     hipStream_t s);
 // r = w(P x - z); prim2/dual2 partials; u += r (UX variant update_u fused with the residual)
 void launch_resid_update_u(const GroupDev& g, const double* xfull, const double* xlast, const double* z, double* u,
                            int nf, Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s);
@@ -184,7 +194,7 @@ void launch_aa_reduce(Seg2 G, const double* cur, long long eff, double* dF, doub
                       double* hist_comb = nullptr, int* hist_rej = nullptr, AAMask mask = AAMask());
 void launch_aa_solve(Ctrl* ctrl, const double* red, int nblocks, int m, hipStream_t s);
 void launch_aa_mix(Seg2 G, double* cur, long long eff, double* dF, double* dG, Ctrl* ctrl, Seg2 out, int m,
-                   hipStream_t s);
+                   hipStream_t s, bool narrow = true);
 
 // ---- element-level test hooks (aa_test_* in the C ABI; tests only)
 void launch_test_prox(int op, const double* prm4, const double* in, int n, double* out, int* iters, hipStream_t s);
