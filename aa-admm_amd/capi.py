@@ -25,7 +25,8 @@ EXPORTS = [
     "aa_settings_default", "aa_elastic_create", "aa_elastic_destroy", "aa_elastic_add_nodes", "aa_elastic_add_tets",
     "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
     "aa_elastic_add_obstacle", "aa_elastic_add_mesh_obstacle", "aa_elastic_set_mesh_obstacle_pose",
-    "aa_elastic_get_mesh_obstacle_pose", "aa_elastic_num_obstacles", "aa_elastic_set_obstacle", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
+    "aa_elastic_get_mesh_obstacle_pose", "aa_elastic_set_mesh_obstacle_vertices", "aa_elastic_get_mesh_obstacle_vertices",
+    "aa_elastic_num_obstacles", "aa_elastic_set_obstacle", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
     "aa_elastic_num_nodes", "aa_elastic_get_x", "aa_elastic_get_v", "aa_elastic_set_v", "aa_elastic_get_history",
     "aa_elastic_get_times", "aa_elastic_set_iterations", "aa_elastic_set_x",
     "aa_elastic_runtime", "aa_elastic_bench_iterations", "aa_elastic_kernel_stats", "aa_elastic_local_stats",
@@ -36,7 +37,7 @@ EXPORTS = [
     "aa_geom_add_closeness", "aa_geom_add_laplacians", "aa_geom_add_closenesses", "aa_geom_setup", "aa_geom_solve", "aa_geom_set_stop", "aa_geom_get_solution", "aa_geom_get_history",
     "aa_geom_runtime_info", "aa_geom_closest_points", "aa_geom_bench_iterations", "aa_geom_kernel_stats",
     "aa_test_prox", "aa_test_cod_solve", "aa_test_geom_project", "aa_test_mesh_sdf", "aa_test_collision_prox",
-    "aa_test_mesh_sdf_posed", "aa_test_collision_prox_posed", "aa_test_direct_solve",
+    "aa_test_mesh_sdf_posed", "aa_test_collision_prox_posed", "aa_test_mesh_refit_tables", "aa_test_mesh_sdf_deformed", "aa_test_direct_solve",
 ]
 
 # Geometry constraint types (Geometry/Constraint.h) and SPD solver types (SolverCommon.h)
@@ -373,6 +374,28 @@ class Solver:
         _chk(lib().aa_elastic_get_mesh_obstacle_pose(self.h, C.c_int(mesh_id), _dp(p), C.byref(posed)))
         return p[:9].reshape(3, 3).copy(), p[9:].copy(), bool(posed.value)
 
+    def set_mesh_obstacle_vertices(self, mesh_id, V):
+        """A deforming mesh obstacle: new positions V (n, 3) for the vertices it was added with (same
+        count, same triangles, obstacle frame) for every later step. The BVH, the leaf triangles and
+        the pseudonormals are refitted on the device; no row is taken, nothing is rebuilt and the
+        captured step graph is kept. A refused V (non-finite, a zero-area triangle, a signed volume
+        that is not positive) changes nothing."""
+        n = self.mesh_obstacle_vertices(mesh_id, count_only=True)
+        v = np.ascontiguousarray(V, np.float64).reshape(-1)
+        if len(v) != 3 * n:
+            raise AAError(-1, f"set_mesh_obstacle_vertices: {len(v) // 3} vertices given, the mesh has {n}")
+        _chk(lib().aa_elastic_set_mesh_obstacle_vertices(self.h, C.c_int(mesh_id), _dp(v)))
+
+    def mesh_obstacle_vertices(self, mesh_id, count_only=False):
+        """The vertices (n, 3) of a mesh obstacle in force (count_only: just n)."""
+        n = C.c_int()
+        _chk(lib().aa_elastic_get_mesh_obstacle_vertices(self.h, C.c_int(mesh_id), None, C.byref(n)))
+        if count_only:
+            return n.value
+        v = np.zeros((n.value, 3))
+        _chk(lib().aa_elastic_get_mesh_obstacle_vertices(self.h, C.c_int(mesh_id), _dp(v), None))
+        return v
+
     def num_obstacles(self):
         """Obstacle rows, analytic and mesh, in the shared insertion order."""
         n = C.c_int()
@@ -573,6 +596,11 @@ def run_scene(ctx: Context, scene, n_steps=None, comm=None):
             row = np.asarray(poses, np.float64)[min(k, len(poses)) - 1]
             for m in range(row.shape[0]):
                 s.set_mesh_obstacle_pose(m, row[m, :9].reshape(3, 3), row[m, 9:])
+        shapes = getattr(scene, "mesh_obstacle_vertices", None)
+        if shapes:   # deforming obstacles: step k runs against entry k - 1 (the last entry holds on)
+            for m, V in enumerate(shapes[min(k, len(shapes)) - 1]):
+                if V is not None:
+                    s.set_mesh_obstacle_vertices(m, V)
         s.step()
         h = s.history()
         h["x"], h["v"] = s.x, s.v
@@ -841,6 +869,43 @@ def hook_mesh_sdf(ctx: Context, V, F, Q, pose=None):
     _chk(lib().aa_test_mesh_sdf(ctx.h, _dp(v), C.c_int(len(v) // 3), _ip(f), C.c_int(len(f) // 3), _dp(q), C.c_int(n),
                                 _dp(c), _dp(dx), _ip(tri)))
     return c, dx, tri
+
+
+def hook_mesh_refit_tables(ctx, V, F, V_new=None, device=1):
+    """The tables of the mesh obstacle (V, F), refitted to V_new when given: dict of nodes (n_nodes,
+    128) uint8, tris (m, 9), pn (m, 21), orig (m,), lo (3,), hi (3,). device = 0: the host
+    restatement (ctx may be None); 1: what the kernels wrote."""
+    v = np.ascontiguousarray(V, np.float64).reshape(-1)
+    f = np.ascontiguousarray(F, np.int32).reshape(-1)
+    w = None if V_new is None else np.ascontiguousarray(V_new, np.float64).reshape(-1)
+    if w is not None and len(w) != len(v):
+        raise ValueError("hook_mesh_refit_tables: V_new must have V's shape")
+    m = len(f) // 3
+    h = ctx.h if ctx is not None else None
+    nodes = np.zeros((2 * max(m, 1), 128), np.uint8)   # a leaf holds a triangle at least: fewer than 2 m nodes
+    tris, pn, orig, lohi, nn = np.zeros((m, 9)), np.zeros((m, 21)), np.zeros(m, np.int32), np.zeros(6), C.c_int()
+    _chk(lib().aa_test_mesh_refit_tables(h, _dp(v), C.c_int(len(v) // 3), _ip(f), C.c_int(m), None if w is None else _dp(w),
+                                         C.c_int(device), nodes.ctypes.data_as(C.c_void_p), _dp(tris), _dp(pn), _ip(orig),
+                                         _dp(lohi), C.byref(nn)))
+    return dict(nodes=nodes[:nn.value].copy(), tris=tris, pn=pn, orig=orig, lo=lohi[:3].copy(), hi=lohi[3:].copy())
+
+
+def hook_mesh_sdf_deformed(ctx: Context, V, F, V_new, Q, pose=None, timings=False):
+    """hook_mesh_sdf on the mesh built from (V, F) and refitted on the device to V_new. timings: a
+    fourth result, the ms of (host prepare + upload of (V_new, F) from scratch, the device refit, the
+    signed-distance kernel on the refitted tree, the same on a freshly built tree)."""
+    v = np.ascontiguousarray(V, np.float64).reshape(-1)
+    w = np.ascontiguousarray(V_new, np.float64).reshape(-1)
+    if len(w) != len(v):
+        raise ValueError("hook_mesh_sdf_deformed: V_new must have V's shape")
+    f = np.ascontiguousarray(F, np.int32).reshape(-1)
+    q = np.ascontiguousarray(Q, np.float64).reshape(-1, 3)
+    n = q.shape[0]
+    c, dx, tri, ms = np.zeros((n, 3)), np.zeros(n), np.zeros(n, np.int32), np.zeros(4)
+    _chk(lib().aa_test_mesh_sdf_deformed(ctx.h, _dp(v), C.c_int(len(v) // 3), _ip(f), C.c_int(len(f) // 3), _dp(w),
+                                         None if pose is None else _dp(_pose_arg(pose)), _dp(q), C.c_int(n), _dp(c), _dp(dx),
+                                         _ip(tri), _dp(ms) if timings else None))
+    return (c, dx, tri, ms) if timings else (c, dx, tri)
 
 
 def hook_collision_prox(ctx: Context, obstacles, meshes, Q, poses=None):

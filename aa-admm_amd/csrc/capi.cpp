@@ -1,6 +1,7 @@
 // extern "C" boundary (include/aa_admm.h). Every entry point catches and maps exceptions to
 // status codes; the message is kept per thread for aa_last_error().
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <exception>
 #include <memory>
@@ -213,6 +214,22 @@ int aa_elastic_get_mesh_obstacle_pose(aa_elastic h, int mesh_id, double pose12[1
         NEED(h, "null handle");
         const bool p = h->s->mesh_obstacle_pose(mesh_id, pose12);
         if (posed) *posed = p ? 1 : 0;
+    });
+}
+
+int aa_elastic_set_mesh_obstacle_vertices(aa_elastic h, int mesh_id, const double* verts3) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
+        h->s->set_mesh_obstacle_vertices(mesh_id, verts3);
+    });
+}
+
+int aa_elastic_get_mesh_obstacle_vertices(aa_elastic h, int mesh_id, double* verts3, int* n_verts) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        const int n = h->s->mesh_obstacle_vertices(mesh_id, verts3);
+        if (n_verts) *n_verts = n;
     });
 }
 
@@ -602,6 +619,116 @@ extern "C" int aa_test_mesh_sdf_posed(aa_ctx ctx, const double* verts3, int n_ve
         AA_HIP(hipMemcpyAsync(dx, ddx.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
         AA_HIP(hipMemcpyAsync(tri, dt.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
         AA_HIP(hipStreamSynchronize(s));
+    });
+}
+
+extern "C" int aa_test_mesh_refit_tables(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
+                                        const double* new_verts3, int device, void* nodes_bytes, double* tris9,
+                                        double* pn21, int* orig, double* lohi6, int* n_nodes) {
+    auto give = [&](const aa::MeshObstacleHost& M) {
+        if (nodes_bytes) std::memcpy(nodes_bytes, M.nodes.data(), sizeof(aa::BvhNode) * M.nodes.size());
+        if (tris9) std::memcpy(tris9, M.tris.data(), sizeof(aa::BvhTri) * M.tris.size());
+        if (pn21) std::copy(M.pn.begin(), M.pn.end(), pn21);
+        if (orig) std::copy(M.orig.begin(), M.orig.end(), orig);
+        if (lohi6) for (int d = 0; d < 3; ++d) { lohi6[d] = M.lo[d]; lohi6[3 + d] = M.hi[d]; }
+        if (n_nodes) *n_nodes = (int)M.nodes.size();
+    };
+    const std::string who = "aa_test_mesh_refit_tables: ";
+    if (!device)
+        return guarded([&] {
+            aa::MeshObstacleHost M = aa::prepare_mesh_obstacle(verts3, n_verts, tris3, n_tris);
+            if (new_verts3) {
+                const aa::MeshRefitTables T = aa::make_refit_tables(M, n_verts, tris3, n_tris);
+                double lo[3], hi[3];
+                aa::validate_mesh_refit(T, new_verts3, who, lo, hi);
+                aa::refit_mesh_obstacle_host(M, T, new_verts3);
+            }
+            give(M);
+        });
+    return with_device_arrays(ctx, [&](hipStream_t s) {
+        aa::MeshObstacleHost M = aa::prepare_mesh_obstacle(verts3, n_verts, tris3, n_tris);
+        aa::MeshObsBuffers buf;
+        buf.upload(M, s);
+        if (new_verts3) {
+            buf.keep_for_refit(M, verts3, n_verts, tris3, n_tris, s);
+            validate_mesh_refit(buf.tables, new_verts3, who, M.lo, M.hi);
+            buf.refit(new_verts3, s);
+        }
+        AA_HIP(hipMemcpyAsync(M.nodes.data(), buf.nodes.p, buf.nodes.bytes(), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(M.tris.data(), buf.tris.p, buf.tris.bytes(), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(M.pn.data(), buf.pn.p, buf.pn.bytes(), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(M.orig.data(), buf.orig.p, buf.orig.bytes(), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipStreamSynchronize(s));
+        give(M);
+    });
+}
+
+namespace {
+// median of 5 event-timed runs of f on s after one warm-up, in ms
+template <class F>
+double median5_ms(hipStream_t s, F&& f) {
+    hipEvent_t e0, e1;
+    AA_HIP(hipEventCreate(&e0));
+    AA_HIP(hipEventCreate(&e1));
+    float t[5];
+    f();
+    AA_HIP(hipStreamSynchronize(s));
+    for (int r = 0; r < 5; ++r) {
+        AA_HIP(hipEventRecord(e0, s));
+        f();
+        AA_HIP(hipEventRecord(e1, s));
+        AA_HIP(hipEventSynchronize(e1));
+        AA_HIP(hipEventElapsedTime(&t[r], e0, e1));
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    std::sort(t, t + 5);
+    return t[2];
+}
+}  // namespace
+
+extern "C" int aa_test_mesh_sdf_deformed(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
+                                        const double* new_verts3, const double* pose12, const double* q3, int n,
+                                        double* closest3, double* dx, int* tri, double* ms4) {
+    return with_device_arrays(ctx, [&](hipStream_t s) {
+        const std::string who = "aa_test_mesh_sdf_deformed: ";
+        NEED(new_verts3 && q3 && closest3 && dx && tri && n >= 0, "aa_test_mesh_sdf_deformed: bad argument");
+        const aa::MeshObstacleHost M = aa::prepare_mesh_obstacle(verts3, n_verts, tris3, n_tris);
+        if (pose12) aa::validate_mesh_pose(pose12, who);
+        aa::MeshObsBuffers buf;
+        aa::MeshObsDev d = buf.upload(M, s);
+        buf.keep_for_refit(M, verts3, n_verts, tris3, n_tris, s);
+        validate_mesh_refit(buf.tables, new_verts3, who, d.lo, d.hi);
+        buf.refit(new_verts3, s);
+        aa::apply_mesh_pose(d, pose12);
+        aa::DevBuf<aa::MeshObsDev> dd;
+        dd.upload(&d, 1, s);
+        aa::DevBuf<double> dq, dc((size_t)3 * std::max(n, 1)), ddx(std::max(n, 1));
+        aa::DevBuf<int> dt(std::max(n, 1));
+        dq.upload(q3, (size_t)3 * n, s);
+        aa::launch_test_mesh_sdf(dd.p, dq.p, n, dc.p, ddx.p, dt.p, s);
+        AA_HIP(hipMemcpyAsync(closest3, dc.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(dx, ddx.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(tri, dt.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+        AA_HIP(hipStreamSynchronize(s));
+        if (!ms4) return;
+        // 1: what the parent offers instead -- prepare on the host and upload, from scratch (wall)
+        aa::MeshObsBuffers fresh;
+        aa::MeshObsDev df;
+        const auto t0 = std::chrono::steady_clock::now();
+        {
+            const aa::MeshObstacleHost Mf = aa::prepare_mesh_obstacle(new_verts3, n_verts, tris3, n_tris);
+            df = fresh.upload(Mf, s);
+            AA_HIP(hipStreamSynchronize(s));
+        }
+        ms4[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        aa::apply_mesh_pose(df, pose12);
+        aa::DevBuf<aa::MeshObsDev> ddf;
+        ddf.upload(&df, 1, s);
+        // 2: the device refit (staging copy included); 3, 4: the walk on the refitted / the fresh tree
+        ms4[1] = median5_ms(s, [&] { buf.refit(new_verts3, s); });
+        ms4[2] = median5_ms(s, [&] { aa::launch_test_mesh_sdf(dd.p, dq.p, n, dc.p, ddx.p, dt.p, s); });
+        ms4[3] = median5_ms(s, [&] { aa::launch_test_mesh_sdf(ddf.p, dq.p, n, dc.p, ddx.p, dt.p, s); });
     });
 }
 

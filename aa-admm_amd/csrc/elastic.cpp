@@ -217,6 +217,29 @@ bool ElasticSolver::mesh_obstacle_pose(int mesh_id, double* pose12) const {
     return d.posed != 0;
 }
 
+void ElasticSolver::set_mesh_obstacle_vertices(int mesh_id, const double* V3) {
+    const std::string who = "set_mesh_obstacle_vertices: ";
+    if (mesh_id < 0 || mesh_id >= (int)meshes_.size())
+        throw Error(ERR_ARG, who + "unknown mesh id " + std::to_string(mesh_id) + " (" + std::to_string(meshes_.size()) + " meshes)");
+    MeshObsBuffers& mo = *meshes_[mesh_id];
+    double lo[3], hi[3];
+    validate_mesh_refit(mo.tables, V3, who, lo, hi);   // throws before anything is touched
+    MeshObsDev& d = mesh_rows_[mesh_id];
+    mo.refit(V3, s());
+    for (int k = 0; k < 3; ++k) { d.lo[k] = lo[k]; d.hi[k] = hi[k]; }
+    AA_HIP(hipMemcpyAsync(mesh_dev_.p + mesh_id, &d, sizeof(d), hipMemcpyHostToDevice, s()));
+    AA_HIP(hipStreamSynchronize(s()));
+    mo.verts.assign(V3, V3 + mo.verts.size());
+}
+
+int ElasticSolver::mesh_obstacle_vertices(int mesh_id, double* V3) const {
+    if (mesh_id < 0 || mesh_id >= (int)meshes_.size())
+        throw Error(ERR_ARG, "get_mesh_obstacle_vertices: unknown mesh id " + std::to_string(mesh_id) + " (" + std::to_string(meshes_.size()) + " meshes)");
+    const std::vector<double>& v = meshes_[mesh_id]->verts;
+    if (V3) std::copy(v.begin(), v.end(), V3);
+    return (int)v.size() / 3;
+}
+
 // PassiveMesh: validated and prepared on the host (mesh_obstacle.hpp), uploaded here, and entered
 // in the obstacle list as a row {OBS_MESH, table row}. The first mesh switches the collision
 // group to its mesh-aware kernel, so a graph captured with the plain one is dropped and captured
@@ -228,6 +251,7 @@ int ElasticSolver::add_mesh_obstacle(const double* V3, int nv, const int* F3, in
     const MeshObstacleHost M = prepare_mesh_obstacle(V3, nv, F3, nf);
     auto mo = std::make_unique<MeshObsBuffers>();
     MeshObsDev d = mo->upload(M, s());
+    mo->keep_for_refit(M, V3, nv, F3, nf, s());
     apply_mesh_pose(d, nullptr);
     if (!mesh_dev_.p) mesh_dev_.alloc(kMaxMeshObstacles);
     const int row = (int)meshes_.size();

@@ -13,6 +13,7 @@
 #include "direct_solve.hpp"
 #include "elastic_kernels.hpp"
 #include "mesh_obstacle.hpp"
+#include "mesh_refit.hpp"
 
 namespace aa {
 
@@ -39,6 +40,17 @@ struct MeshObsBuffers {
         for (int k = 0; k < 3; ++k) { d.lo[k] = M.lo[k]; d.hi[k] = M.hi[k]; }
         return d;
     }
+    // Deforming obstacles: what a refit to new vertices needs (mesh_refit.hpp), kept from add time
+    // on, and the vertices in force. refit() enqueues the kernels on s and waits for nothing.
+    MeshRefitTables tables;
+    MeshRefitBuffers rf;
+    std::vector<double> verts;
+    void keep_for_refit(const MeshObstacleHost& M, const double* V3, int nv, const int* F3, int nf, hipStream_t s) {
+        tables = make_refit_tables(M, nv, F3, nf);
+        rf.upload(tables, s);
+        verts.assign(V3, V3 + 3 * (size_t)nv);
+    }
+    void refit(const double* V3, hipStream_t s) { rf.refit(V3, nodes.p, (int)nodes.n, tris.p, pn.p, s); }
 };
 
 class ElasticSolver {
@@ -63,6 +75,12 @@ public:
     // place (index in the shared insertion order; type must match the stored one).
     void set_mesh_obstacle_pose(int mesh_id, const double* pose12);
     bool mesh_obstacle_pose(int mesh_id, double* pose12) const;
+    // Deforming obstacles. New vertex positions for a mesh (same count, same triangles, obstacle
+    // frame): validated on the host, then the BVH's bounds, the leaf triangles and the
+    // pseudonormals refitted in place on the solver's stream (mesh_refit.hip) and the row's root
+    // box rewritten; no buffer moves, so the graph stays. A refused call changes nothing.
+    void set_mesh_obstacle_vertices(int mesh_id, const double* verts3);
+    int mesh_obstacle_vertices(int mesh_id, double* verts3) const;   // returns the vertex count
     int num_obstacles() const { return (int)obstacles_.size(); }
     void set_obstacle(int index, int type, const double* params);
     // WindForce (ExplicitForce.hpp:39-47) on the given triangles; returns its id

@@ -40,11 +40,11 @@ struct MeshObstacleHost {
 };
 
 namespace mesh_detail {
-inline void sub3(const double* a, const double* b, double* r) { r[0] = a[0] - b[0]; r[1] = a[1] - b[1]; r[2] = a[2] - b[2]; }
-inline void cross3(const double* u, const double* w, double* r) {
+AA_HD inline void sub3(const double* a, const double* b, double* r) { r[0] = a[0] - b[0]; r[1] = a[1] - b[1]; r[2] = a[2] - b[2]; }
+AA_HD inline void cross3(const double* u, const double* w, double* r) {
     r[0] = u[1] * w[2] - u[2] * w[1]; r[1] = u[2] * w[0] - u[0] * w[2]; r[2] = u[0] * w[1] - u[1] * w[0];
 }
-inline double dot3(const double* u, const double* w) { return u[0] * w[0] + u[1] * w[1] + u[2] * w[2]; }
+AA_HD inline double dot3(const double* u, const double* w) { return u[0] * w[0] + u[1] * w[1] + u[2] * w[2]; }
 }  // namespace mesh_detail
 
 // Throws Error(ERR_ARG) naming the first offending vertex, triangle or edge.
@@ -179,6 +179,194 @@ inline MeshObstacleHost prepare_mesh_obstacle(const double* V, int nv, const int
                 M.lo[d] = std::min(M.lo[d], v); M.hi[d] = std::max(M.hi[d], v);
             }
     return M;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Deforming obstacles: the refit of a prepared mesh to new vertex positions V' (same vertex count,
+// same triangles). The tree keeps its node order, leaf contents and stored axes; what follows from
+// the positions is recomputed:
+//   tris[k].v    the corners of leaf triangle k read from V';
+//   node boxes   lo[d] = down(min P[d]), hi[d] = up(max P[d]) over the 3 count vertices P of the
+//                node's contiguous range of leaf triangles (BvhBuilder::down / up);
+//   axis ranges  for each stored axis a of nrm, t1, t2 the range of
+//                s = ((double)a[0] P[0] + (double)a[1] P[1]) + (double)a[2] P[2] (left to right, no
+//                FMA contraction), rounded outward alike; a range the build stored as
+//                (-FLT_MAX, FLT_MAX) -- a degenerate patch, AA_CP_OBB=0 -- stays so. The stale axes
+//                are still orthonormal, so box_d2 / box_d2f stay lower bounds: the walk is exact,
+//                the bounds only loosen as the shape leaves the one the tree was built for;
+//   pn           prepare_mesh_obstacle's formulas on V' in a fixed summation order: a vertex's terms
+//                in increasing caller triangle index from 0.0, an edge's (0 + fn[t_lo]) + fn[t_hi];
+//   lo / hi      the exact fp64 range of the referenced vertices.
+// refit_mesh_obstacle_host defines the result; the device kernels (mesh_refit.hip) reproduce it
+// bit for bit except for acos (the corner angles of the vertex sums).
+struct MeshRefitTables {
+    int nv = 0;
+    std::vector<int> F;          // the caller's triangles, [nf][3] (validation runs in their order)
+    std::vector<int> leaf_vid;   // [nf][3] vertex ids of leaf triangle k, the build's corner order
+    std::vector<int> node_beg, node_cnt;   // per node: its contiguous range of leaf triangles
+    // per vertex the (leaf triangle, corner) pairs, 4 k + corner, in increasing CALLER triangle index
+    std::vector<int> vt_ptr, vt;
+    // [nf][3][2], leaf order: the two leaf triangles on edge ab, bc, ca, the lower caller index first
+    std::vector<int> edge_tris;
+    // node-bound reduction of the large nodes (more than kRefitChunk triangles): the nodes, and
+    // their ranges cut into chunks of at most kRefitChunk triangles (big_chunk_ptr: CSR over chunks)
+    std::vector<int> big_node, big_chunk_ptr, chunk_big, chunk_beg, chunk_cnt;
+};
+constexpr int kRefitChunk = 1024;
+
+inline MeshRefitTables make_refit_tables(const MeshObstacleHost& M, int nv, const int* F, int nf) {
+    MeshRefitTables T;
+    T.nv = nv;
+    T.F.assign(F, F + 3 * (size_t)nf);
+    std::vector<int> leaf_of(nf);   // caller triangle -> leaf position
+    T.leaf_vid.resize(3 * (size_t)nf);
+    for (int k = 0; k < nf; ++k) {
+        leaf_of[M.orig[k]] = k;
+        for (int a = 0; a < 3; ++a) T.leaf_vid[3 * (size_t)k + a] = F[3 * (size_t)M.orig[k] + a];
+    }
+    const int nn = (int)M.nodes.size();
+    T.node_beg.resize(nn); T.node_cnt.resize(nn);
+    for (int i = nn - 1; i >= 0; --i) {   // children come after their parent in the depth-first order
+        const BvhNode& nd = M.nodes[i];
+        if (bvh_count(nd)) { T.node_beg[i] = nd.a; T.node_cnt[i] = bvh_count(nd); }
+        else { T.node_beg[i] = T.node_beg[i + 1]; T.node_cnt[i] = T.node_beg[nd.a] + T.node_cnt[nd.a] - T.node_beg[i + 1]; }
+    }
+    T.vt_ptr.assign((size_t)nv + 1, 0);
+    for (size_t i = 0; i < 3 * (size_t)nf; ++i) ++T.vt_ptr[F[i] + 1];
+    for (int i = 0; i < nv; ++i) T.vt_ptr[i + 1] += T.vt_ptr[i];
+    T.vt.resize(3 * (size_t)nf);
+    std::vector<int> fill(T.vt_ptr.begin(), T.vt_ptr.end() - 1);
+    std::map<std::pair<int, int>, std::pair<int, int>> et;   // edge -> its two caller triangles, lower first
+    for (int t = 0; t < nf; ++t)
+        for (int a = 0; a < 3; ++a) {
+            const int p = F[3 * (size_t)t + a], q = F[3 * (size_t)t + (a + 1) % 3];
+            T.vt[fill[p]++] = 4 * leaf_of[t] + a;
+            auto it = et.find({std::min(p, q), std::max(p, q)});
+            if (it == et.end()) et[{std::min(p, q), std::max(p, q)}] = {t, -1};
+            else it->second.second = t;
+        }
+    T.edge_tris.resize(6 * (size_t)nf);
+    for (int k = 0; k < nf; ++k)
+        for (int a = 0; a < 3; ++a) {
+            const int p = T.leaf_vid[3 * (size_t)k + a], q = T.leaf_vid[3 * (size_t)k + (a + 1) % 3];
+            const auto& e = et[{std::min(p, q), std::max(p, q)}];
+            T.edge_tris[6 * (size_t)k + 2 * a] = leaf_of[e.first];
+            T.edge_tris[6 * (size_t)k + 2 * a + 1] = leaf_of[e.second];
+        }
+    T.big_chunk_ptr.push_back(0);
+    for (int i = 0; i < nn; ++i) {
+        if (T.node_cnt[i] <= kRefitChunk) continue;
+        for (int b = 0; b < T.node_cnt[i]; b += kRefitChunk) {
+            T.chunk_big.push_back((int)T.big_node.size());
+            T.chunk_beg.push_back(T.node_beg[i] + b);
+            T.chunk_cnt.push_back(std::min(kRefitChunk, T.node_cnt[i] - b));
+        }
+        T.big_node.push_back(i);
+        T.big_chunk_ptr.push_back((int)T.chunk_big.size());
+    }
+    return T;
+}
+
+// What a refit checks of V' before anything is touched (the topology is not looked at again):
+// throws Error(ERR_ARG) naming the cause. lo / hi receive the exact range of the referenced vertices.
+inline void validate_mesh_refit(const MeshRefitTables& T, const double* V, const std::string& who, double* lo, double* hi) {
+    using namespace mesh_detail;
+    if (!V) throw Error(ERR_ARG, who + "null vertex array");
+    for (int i = 0; i < T.nv; ++i)
+        for (int d = 0; d < 3; ++d)
+            if (!std::isfinite(V[3 * (size_t)i + d]))
+                throw Error(ERR_ARG, who + "vertex " + std::to_string(i) + " has a non-finite coordinate");
+    const int nf = (int)T.F.size() / 3;
+    double vol6 = 0;
+    for (int d = 0; d < 3; ++d) { lo[d] = DBL_MAX; hi[d] = -DBL_MAX; }
+    for (int t = 0; t < nf; ++t) {
+        const double *A = V + 3 * (size_t)T.F[3 * (size_t)t], *B = V + 3 * (size_t)T.F[3 * (size_t)t + 1],
+                     *C = V + 3 * (size_t)T.F[3 * (size_t)t + 2];
+        double u[3], w[3], n[3];
+        sub3(B, A, u); sub3(C, A, w); cross3(u, w, n);
+        if (!(dot3(n, n) > 0.0)) throw Error(ERR_ARG, who + "triangle " + std::to_string(t) + " has zero area");
+        cross3(B, C, n);
+        vol6 += dot3(A, n);
+        for (const double* P : {A, B, C})
+            for (int d = 0; d < 3; ++d) { lo[d] = std::min(lo[d], P[d]); hi[d] = std::max(hi[d], P[d]); }
+    }
+    if (!(vol6 > 0.0)) throw Error(ERR_ARG, who + "the signed volume is not positive: the deformed surface is turned inside out");
+}
+
+namespace mesh_detail {
+// unit normal and the three clamped corner angles of a triangle (prepare_mesh_obstacle's formulas)
+AA_HD inline void tri_normal_angles(const double* v9, double* fn, double* ang) {
+    double u[3], w[3], n[3];
+    sub3(v9 + 3, v9, u); sub3(v9 + 6, v9, w); cross3(u, w, n);
+    const double l = std::sqrt(dot3(n, n));
+    for (int d = 0; d < 3; ++d) fn[d] = n[d] / l;
+    for (int a = 0; a < 3; ++a) {
+        double e1[3], e2[3];
+        sub3(v9 + 3 * ((a + 1) % 3), v9 + 3 * a, e1);
+        sub3(v9 + 3 * ((a + 2) % 3), v9 + 3 * a, e2);
+        double c = dot3(e1, e2) / std::sqrt(dot3(e1, e1) * dot3(e2, e2));
+        c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
+        ang[a] = std::acos(c);
+    }
+}
+}  // namespace mesh_detail
+
+// The refit itself, on the host: M (as prepared, or as refitted before) taken to the vertices V.
+// V is expected to have passed validate_mesh_refit.
+inline void refit_mesh_obstacle_host(MeshObstacleHost& M, const MeshRefitTables& T, const double* V) {
+    using namespace mesh_detail;
+    const int nf = (int)M.tris.size(), nn = (int)M.nodes.size();
+    std::vector<double> fa(6 * (size_t)nf);   // per leaf triangle: unit normal, three corner angles
+    for (int k = 0; k < nf; ++k) {
+        for (int a = 0; a < 3; ++a)
+            for (int d = 0; d < 3; ++d) M.tris[k].v[3 * a + d] = V[3 * (size_t)T.leaf_vid[3 * (size_t)k + a] + d];
+        tri_normal_angles(M.tris[k].v, &fa[6 * (size_t)k], &fa[6 * (size_t)k + 3]);
+    }
+    static const int corner_slot[3] = {0, 1, 3}, edge_slot[3] = {2, 5, 4};   // a b c; ab bc ca
+    for (int k = 0; k < nf; ++k) {
+        double* P = M.pn.data() + (size_t)kPnStride * k;
+        for (int a = 0; a < 3; ++a) {
+            const int p = T.leaf_vid[3 * (size_t)k + a];
+            double s[3] = {0.0, 0.0, 0.0};
+            for (int j = T.vt_ptr[p]; j < T.vt_ptr[p + 1]; ++j) {
+                const double* f = &fa[6 * (size_t)(T.vt[j] >> 2)];
+                const double ang = f[3 + (T.vt[j] & 3)];
+                for (int d = 0; d < 3; ++d) s[d] += ang * f[d];
+            }
+            const double* f0 = &fa[6 * (size_t)T.edge_tris[6 * (size_t)k + 2 * a]];
+            const double* f1 = &fa[6 * (size_t)T.edge_tris[6 * (size_t)k + 2 * a + 1]];
+            for (int d = 0; d < 3; ++d) {
+                P[3 * corner_slot[a] + d] = s[d];
+                P[3 * edge_slot[a] + d] = (0.0 + f0[d]) + f1[d];
+            }
+        }
+        for (int d = 0; d < 3; ++d) P[18 + d] = fa[6 * (size_t)k + d];
+    }
+    for (int i = 0; i < nn; ++i) {
+        BvhNode& nd = M.nodes[i];
+        const float* axes[3] = {nd.nrm, nd.t1, nd.t2};
+        double lo[6], hi[6];
+        for (int c = 0; c < 6; ++c) { lo[c] = DBL_MAX; hi[c] = -DBL_MAX; }
+        for (int k = T.node_beg[i]; k < T.node_beg[i] + T.node_cnt[i]; ++k)
+            for (int a = 0; a < 3; ++a) {
+                const double* P = M.tris[k].v + 3 * a;
+                for (int d = 0; d < 3; ++d) { lo[d] = std::min(lo[d], P[d]); hi[d] = std::max(hi[d], P[d]); }
+                for (int x = 0; x < 3; ++x) {
+                    const double s = ((double)axes[x][0] * P[0] + (double)axes[x][1] * P[1]) + (double)axes[x][2] * P[2];
+                    lo[3 + x] = std::min(lo[3 + x], s); hi[3 + x] = std::max(hi[3 + x], s);
+                }
+            }
+        for (int d = 0; d < 3; ++d) { nd.lo[d] = BvhBuilder::down(lo[d]); nd.hi[d] = BvhBuilder::up(hi[d]); }
+        float* rl[3] = {&nd.dlo, &nd.t1lo, &nd.t2lo};
+        float* rh[3] = {&nd.dhi, &nd.t1hi, &nd.t2hi};
+        for (int x = 0; x < 3; ++x) {
+            if (*rl[x] == -FLT_MAX && *rh[x] == FLT_MAX) continue;   // stored unbounded: stays so
+            *rl[x] = BvhBuilder::down(lo[3 + x]); *rh[x] = BvhBuilder::up(hi[3 + x]);
+        }
+    }
+    for (int d = 0; d < 3; ++d) { M.lo[d] = DBL_MAX; M.hi[d] = -DBL_MAX; }
+    for (int k = 0; k < nf; ++k)
+        for (int c = 0; c < 9; ++c) { M.lo[c % 3] = std::min(M.lo[c % 3], M.tris[k].v[c]); M.hi[c % 3] = std::max(M.hi[c % 3], M.tris[k].v[c]); }
 }
 
 }  // namespace aa

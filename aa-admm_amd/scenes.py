@@ -101,6 +101,11 @@ class Scene:
     # world) then t; the scene runner sets row k - 1 before step k, where it advances the moving
     # pins (capi.run_scene). None = the meshes stay as given.
     mesh_obstacle_poses: Optional[np.ndarray] = None
+    # deforming mesh obstacles: a list over steps, each entry a list over meshes of (nv, 3) vertex
+    # arrays (the mesh's own vertex count and triangles) or None for "leave as is"; step k runs
+    # against entry k - 1 and the last entry holds on (capi.run_scene, after the poses). None = the
+    # meshes keep their shape.
+    mesh_obstacle_vertices: Optional[list] = None
     winds: list = dataclasses.field(default_factory=list)
 
     @property
@@ -529,9 +534,10 @@ def torus_mesh(nu=16, nv=8, R=1.0, r=0.4, center=(0.0, 0.0, 0.0)):
     return V, np.asarray(F, np.int32)
 
 
-def cloth_on_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15) -> Scene:
+def cloth_on_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15, ring=0.3) -> Scene:
     """Demo of the mesh obstacle: an unpinned cloth sheet dropped flat onto a torus lying in the
-    x-z plane ((u,x) variant; every node collision-checked)."""
+    x-z plane ((u,x) variant; every node collision-checked). The torus' major radius is `ring` times
+    the sheet's side, its tube radius 0.4 of that."""
     sc = cloth(nx, ny, variant=VARIANT_H, aa_m=aa_m, iters=iters, n_steps=n_steps, accel=accel)
     sc.name = "cloth_on_torus"
     x = np.array(sc.x, np.float64)
@@ -541,7 +547,7 @@ def cloth_on_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=
         x[:, [flat, 1]] = x[:, [1, flat]]
     ctr = 0.5 * (x.max(0) + x.min(0))
     x = x - ctr
-    R = 0.3 * float(max(ext))
+    R = ring * float(max(ext))
     r = 0.4 * R
     x[:, 1] = r + drop
     sc.x = x
@@ -568,4 +574,19 @@ def cloth_on_spinning_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=
     for k in range(n_steps):
         poses[k, 0, :9] = rotation_y((k + 1) * dtheta).reshape(9)
     sc.mesh_obstacle_poses = poses
+    return sc
+
+
+def cloth_on_breathing_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15, amplitude=0.25,
+                             period=20, ring=0.42) -> Scene:
+    """Demo of the deforming mesh obstacle: cloth_on_torus -- with a ring wide enough that the middle
+    of the sheet's edges comes to lie on the tube while the corners hang free -- and the torus' tube
+    radius oscillating, r_k = r (1 + amplitude sin^2(pi k / period)) in step k: never below the
+    radius r the torus is added with, and at its largest in steps period / 2, 3 period / 2, ..."""
+    sc = cloth_on_torus(nx, ny, iters=iters, aa_m=aa_m, accel=accel, n_steps=n_steps, drop=drop, ring=ring)
+    sc.name = "cloth_on_breathing_torus"
+    R = ring * float(max(sc.x.max(0) - sc.x.min(0)))
+    r = 0.4 * R
+    sc.mesh_obstacle_vertices = [[torus_mesh(16, 8, R, r * (1.0 + amplitude * np.sin(np.pi * k / period) ** 2))[0]]
+                                 for k in range(1, n_steps + 1)]
     return sc

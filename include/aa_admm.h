@@ -176,6 +176,43 @@ int aa_elastic_add_mesh_obstacle(aa_elastic h, const double* verts3, int n_verts
  * one is set; either output may be NULL. */
 int aa_elastic_set_mesh_obstacle_pose(aa_elastic h, int mesh_id, const double pose12[12]);
 int aa_elastic_get_mesh_obstacle_pose(aa_elastic h, int mesh_id, double pose12[12], int* posed);
+/* Deforming obstacles: new vertex positions for mesh obstacle mesh_id -- 3 n_verts doubles, the
+ * vertex count and the triangles of aa_elastic_add_mesh_obstacle, in the obstacle frame (a pose set
+ * for the mesh still applies on top). Changed as often as every step without a host BVH build and
+ * without a new obstacle or mesh row: the topology is not validated again and the BVH is not
+ * rebuilt -- the tree keeps its node order, its leaf contents and its stored axes -- but refitted on
+ * the device to the new positions V', in this order:
+ *   leaf triangles: the corners read from V' in the build's leaf and corner order;
+ *   pseudonormals: the formulas of aa_elastic_add_mesh_obstacle on V' (unit face normals, clamped
+ *     acos corner angles), a vertex's terms added in increasing triangle index from 0, an edge's
+ *     value (0 + n[t_lo]) + n[t_hi];
+ *   node bounds: per node the box of the vertices of its triangles and the ranges of
+ *     s = (a0 P0 + a1 P1) + a2 P2 (fp64, no FMA contraction) along its three stored axes a, each
+ *     rounded outward to fp32; a range stored as unbounded stays so;
+ *   the row's fp64 root box: the exact range of the referenced vertices.
+ * The closest-point walk is exact for any conservative bounds, so the answers are those of a mesh
+ * freshly added with V' (bit for bit where the closest triangle is unique); only the walk's cost
+ * grows as the shape leaves the one the tree was built for. Measured on a 200 k triangle torus
+ * (DESIGN.md section 3.7): the refit takes 0.47 ms where preparing and uploading the mesh anew
+ * takes 300 ms on the host; the walk on the refitted tree costs what the fresh tree's costs for an
+ * unchanged shape, 2.2 times that after a twist, bend and stretch that moves vertices by up to 15 %
+ * of the torus' diameter, and 4.8 times after one that moves them by up to 31 %. More than twice the fresh
+ * walk is the point where a caller should add the new shape as a new mesh (a host build and a new
+ * row) rather than go on refitting -- shapes that stay near the added one, a breathing or
+ * flexing body, are far from it. May be called before
+ * or after initialize and between steps; the work runs on the solver's stream and is finished when
+ * the call returns; every device buffer and the mesh's table row keep their addresses, so the
+ * captured step graph is kept. The vertices hold for every ADMM iteration of every later step until
+ * changed. The obstacle stays kinematic: it has no velocity and exerts no friction. Validation
+ * happens on the host before anything on the device is touched, and a refused call leaves the
+ * obstacle exactly as it was. AA_ERR_ARG, the message naming the cause: an unknown mesh_id, a null
+ * pointer, a non-finite coordinate (the vertex named), a zero-area triangle (named; the test of
+ * aa_elastic_add_mesh_obstacle), a signed volume that is not positive. Partitioned solvers: every
+ * rank makes the same call, as for the pose.
+ * aa_elastic_get_mesh_obstacle_vertices returns the vertices in force (verts3 may be NULL) and
+ * their count (n_verts may be NULL). */
+int aa_elastic_set_mesh_obstacle_vertices(aa_elastic h, int mesh_id, const double* verts3);
+int aa_elastic_get_mesh_obstacle_vertices(aa_elastic h, int mesh_id, double* verts3, int* n_verts);
 /* The number of obstacle rows, analytic and mesh, in the shared insertion order. */
 int aa_elastic_num_obstacles(aa_elastic h, int* n);
 /* Re-parameterises the analytic obstacle at position `index` of that order (a rising floor, a
@@ -384,7 +421,18 @@ int aa_geom_set_comm(aa_geom h, aa_comm c);
  *   aa_test_mesh_sdf_posed / aa_test_collision_prox_posed: the same with kinematic poses
  *     (aa_elastic_set_mesh_obstacle_pose; validated alike): pose12 for the one mesh, mesh_poses =
  *     12 doubles per mesh (twelve NaNs: that mesh unposed); NULL = unposed. Queries and the reported closest point are in the
- *     world frame, dx is the obstacle-frame distance. */
+ *     world frame, dx is the obstacle-frame distance.
+ *   aa_test_mesh_refit_tables: the tables of a mesh obstacle built from verts3 / tris3 and, when
+ *     new_verts3 is given, refitted to it (aa_elastic_set_mesh_obstacle_vertices; validated alike):
+ *     device = 0 the host restatement (ctx may be NULL), 1 what the kernels wrote, downloaded.
+ *     Outputs, each optional: the n_nodes 128-byte node records, the leaf triangles (9 doubles
+ *     each), the pseudonormal table (21 each), the leaf order -> caller triangle map, the root box
+ *     (lo then hi) and the node count (at most n_tris).
+ *   aa_test_mesh_sdf_deformed: aa_test_mesh_sdf_posed on the mesh built from verts3 and refitted on
+ *     the device to new_verts3. ms4 (optional) receives four times in ms: host preparation plus
+ *     upload of the deformed mesh from scratch (wall), the device refit, the signed-distance kernel
+ *     on the refitted tree and on a freshly built tree of the same shape (the last three by device
+ *     events, the median of 5 runs after a warm-up). */
 int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double* in, int n, double* out, int* iters);
 int aa_test_cod_solve(aa_ctx ctx, int k, const double* M, const double* b, double* theta);
 int aa_test_geom_project(aa_ctx ctx, int type, int k, const double* prm2, const double* in, int n, double* out);
@@ -398,6 +446,12 @@ int aa_test_mesh_sdf_posed(aa_ctx ctx, const double* verts3, int n_verts, const 
 int aa_test_collision_prox_posed(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
                                  const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr, int n_meshes,
                                  const double* mesh_poses, const double* q3, int n, double* out3);
+int aa_test_mesh_refit_tables(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
+                              const double* new_verts3, int device, void* nodes_bytes, double* tris9, double* pn21,
+                              int* orig, double* lohi6, int* n_nodes);
+int aa_test_mesh_sdf_deformed(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
+                              const double* new_verts3, const double* pose12, const double* q3, int n,
+                              double* closest3, double* dx, int* tri, double* ms4);
 /* The global step's sparse triangular solve alone (DirectSolver, csrc/direct_solve.hpp), on a
  * caller-given SPD matrix: full-pattern symmetric CSR (ptr, col, val; sorted columns, every
  * diagonal stored) of order n in the caller's ordering, node coordinates xyz3.

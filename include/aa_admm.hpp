@@ -14,6 +14,7 @@
 //   solver.initialize(settings);                       // Solver::initialize (returns bool)
 //   solver.step();                                     // Solver::step; solver.m_x / m_v updated
 //   solver.set_obstacle_pose(mesh, R, t); solver.update_obstacle(floor);   // kinematic obstacles, between steps
+//   solver.set_obstacle_vertices(mesh, new_verts);                         // a mesh that changes shape
 //
 // Energy terms are descriptors of the built-in element kinds (batched SoA on the device);
 // user-defined EnergyTerm subclasses with arbitrary prox() are not supported (no host
@@ -303,6 +304,15 @@ public:
         for (int i = 0; i < 9; ++i) p[i] = R[i];
         for (int i = 0; i < 3; ++i) p[9 + i] = t ? t[i] : 0.0;
         check(aa_elastic_set_mesh_obstacle_pose(h_, mesh->mesh_id, p));
+    }
+    // Deforming obstacles (no reference counterpart; aa_admm.h, aa_elastic_set_mesh_obstacle_vertices):
+    // new positions for the mesh's vertices (same count, same triangles, obstacle frame) for every
+    // later step until changed -- a breathing body under a cloth. mesh->verts is updated too.
+    void set_obstacle_vertices(const std::shared_ptr<PassiveMesh>& mesh, const std::vector<double>& verts3) {
+        if (!mesh || mesh->mesh_id < 0 || row_of(mesh.get()) < 0) throw std::runtime_error("set_obstacle_vertices: the mesh was not added to this solver");
+        if (verts3.size() != mesh->verts.size()) throw std::runtime_error("set_obstacle_vertices: the vertex count differs from the mesh's");
+        check(aa_elastic_set_mesh_obstacle_vertices(h_, mesh->mesh_id, verts3.data()));
+        mesh->verts = verts3;
     }
     // ... and the analytic shapes: change obj->params, then call this to re-send them to the row
     // the obstacle was added as
