@@ -26,6 +26,7 @@ EXPORTS = [
     "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
     "aa_elastic_add_obstacle", "aa_elastic_add_mesh_obstacle", "aa_elastic_set_mesh_obstacle_pose",
     "aa_elastic_get_mesh_obstacle_pose", "aa_elastic_set_mesh_obstacle_vertices", "aa_elastic_get_mesh_obstacle_vertices",
+    "aa_elastic_bind_mesh_obstacle", "aa_elastic_mesh_obstacle_status", "aa_elastic_set_mesh_obstacle_exempt",
     "aa_elastic_num_obstacles", "aa_elastic_set_obstacle", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
     "aa_elastic_num_nodes", "aa_elastic_get_x", "aa_elastic_get_v", "aa_elastic_set_v", "aa_elastic_get_history",
     "aa_elastic_get_times", "aa_elastic_set_iterations", "aa_elastic_set_x",
@@ -38,6 +39,7 @@ EXPORTS = [
     "aa_geom_runtime_info", "aa_geom_closest_points", "aa_geom_bench_iterations", "aa_geom_kernel_stats",
     "aa_test_prox", "aa_test_cod_solve", "aa_test_geom_project", "aa_test_mesh_sdf", "aa_test_collision_prox",
     "aa_test_mesh_sdf_posed", "aa_test_collision_prox_posed", "aa_test_mesh_refit_tables", "aa_test_mesh_sdf_deformed", "aa_test_direct_solve",
+    "aa_test_bound_refit", "aa_test_collision_prox_exempt",
 ]
 
 # Geometry constraint types (Geometry/Constraint.h) and SPD solver types (SolverCommon.h)
@@ -396,6 +398,31 @@ class Solver:
         _chk(lib().aa_elastic_get_mesh_obstacle_vertices(self.h, C.c_int(mesh_id), _dp(v), None))
         return v
 
+    def bind_mesh_obstacle(self, mesh_id, nodes):
+        """A bound mesh obstacle: vertex i of the mesh follows solver node nodes[i] (any node). Every
+        later step starts by gathering the vertices from its start state on the device, checking the
+        shape there and refitting; the obstacle holds that shape for the step's iterations. A shape
+        that fails the check (mesh_obstacle_status) is skipped and the last good one stays.
+        nodes None: unbind, the shape last in force stays."""
+        if nodes is None:
+            _chk(lib().aa_elastic_bind_mesh_obstacle(self.h, C.c_int(mesh_id), None, C.c_int(0)))
+            return
+        i = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        _chk(lib().aa_elastic_bind_mesh_obstacle(self.h, C.c_int(mesh_id), _ip(i), C.c_int(len(i))))
+
+    def mesh_obstacle_status(self, mesh_id):
+        """dict(bound, refits, skipped, last_cause): refits taken and skipped since binding and the
+        cause of the last skipped one (0 none, 1 non-finite, 2 zero area, 3 signed volume)."""
+        b, r, k, c = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _chk(lib().aa_elastic_mesh_obstacle_status(self.h, C.c_int(mesh_id), C.byref(b), C.byref(r), C.byref(k), C.byref(c)))
+        return dict(bound=bool(b.value), refits=r.value, skipped=k.value, last_cause=c.value)
+
+    def set_mesh_obstacle_exempt(self, mesh_id, nodes):
+        """The collision terms of `nodes` skip this mesh as if it were not in the obstacle list.
+        Replaces the earlier list; empty or None clears it."""
+        i = np.ascontiguousarray([] if nodes is None else nodes, np.int32).reshape(-1)
+        _chk(lib().aa_elastic_set_mesh_obstacle_exempt(self.h, C.c_int(mesh_id), _ip(i) if len(i) else None, C.c_int(len(i))))
+
     def num_obstacles(self):
         """Obstacle rows, analytic and mesh, in the shared insertion order."""
         n = C.c_int()
@@ -573,6 +600,12 @@ def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
         s.set_collisions(scene.collision_idx)
     for tris, direction in getattr(scene, "winds", []):
         s.add_wind(tris, direction)
+    for m, nodes in enumerate(getattr(scene, "mesh_obstacle_bindings", None) or []):
+        if nodes is not None:
+            s.bind_mesh_obstacle(m, nodes)
+    for m, nodes in enumerate(getattr(scene, "mesh_obstacle_exempt", None) or []):
+        if nodes is not None:
+            s.set_mesh_obstacle_exempt(m, nodes)
     return s
 
 
@@ -888,6 +921,71 @@ def hook_mesh_refit_tables(ctx, V, F, V_new=None, device=1):
                                          C.c_int(device), nodes.ctypes.data_as(C.c_void_p), _dp(tris), _dp(pn), _ip(orig),
                                          _dp(lohi), C.byref(nn)))
     return dict(nodes=nodes[:nn.value].copy(), tris=tris, pn=pn, orig=orig, lo=lohi[:3].copy(), hi=lohi[3:].copy())
+
+
+def hook_bound_refit(ctx, V, F, X, nodes, device=1, timing=False, X_first=None):
+    """aa_test_bound_refit: the mesh (V, F), its vertices gathered as X[nodes] from the node array X
+    (n, 3), checked and -- when the check passes -- refitted. hook_mesh_refit_tables' dict plus
+    taken (bool), cause (0..3) and vol6. device = 0: the host restatement (ctx may be None).
+    X_first: a bound refit from these positions runs first, as an earlier step's would (its status is
+    not reported). timing (device = 1): also ms, the device time of gather + check + refit (median of 5)."""
+    v = np.ascontiguousarray(V, np.float64).reshape(-1)
+    f = np.ascontiguousarray(F, np.int32).reshape(-1)
+    x = np.ascontiguousarray(X, np.float64).reshape(-1)
+    i = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+    if 3 * len(i) != len(v):
+        raise ValueError("hook_bound_refit: one node per vertex")
+    m = len(f) // 3
+    h = ctx.h if ctx is not None else None
+    nd = np.zeros((2 * max(m, 1), 128), np.uint8)
+    tris, pn, orig, lohi, nn = np.zeros((m, 9)), np.zeros((m, 21)), np.zeros(m, np.int32), np.zeros(6), C.c_int()
+    st, vol6, ms = np.zeros(2, np.int32), C.c_double(), C.c_double()
+    x0 = None if X_first is None else np.ascontiguousarray(X_first, np.float64).reshape(-1)
+    if x0 is not None and len(x0) != len(x):
+        raise ValueError("hook_bound_refit: X_first must have X's shape")
+    _chk(lib().aa_test_bound_refit(h, _dp(v), C.c_int(len(v) // 3), _ip(f), C.c_int(m), _dp(x), C.c_int(len(x) // 3), _ip(i),
+                                   C.c_int(device), nd.ctypes.data_as(C.c_void_p), _dp(tris), _dp(pn), _ip(orig), _dp(lohi),
+                                   C.byref(nn), _ip(st), C.byref(vol6), C.byref(ms) if timing else None,
+                                   None if x0 is None else _dp(x0)))
+    out = dict(nodes=nd[:nn.value].copy(), tris=tris, pn=pn, orig=orig, lo=lohi[:3].copy(), hi=lohi[3:].copy(),
+               taken=bool(st[0]), cause=int(st[1]), vol6=float(vol6.value))
+    if timing:
+        out["ms"] = float(ms.value)
+    return out
+
+
+def hook_collision_prox_exempt(ctx: Context, obstacles, meshes, Q, q_nodes, exempt, poses=None):
+    """hook_collision_prox with the node of every query (q_nodes (n,)) and, per mesh, the nodes
+    exempt from it (exempt: one list or None per mesh)."""
+    rows = np.zeros((len(obstacles), 8))
+    for k, (kind, prm) in enumerate(obstacles):
+        a = np.asarray(prm, np.float64).reshape(-1)
+        rows[k, 0] = kind
+        rows[k, 1:1 + len(a)] = a
+    vs = [np.ascontiguousarray(V, np.float64).reshape(-1, 3) for V, _ in meshes]
+    fs = [np.ascontiguousarray(F, np.int32).reshape(-1, 3) for _, F in meshes]
+    vptr = np.concatenate([[0], np.cumsum([len(v) for v in vs])]).astype(np.int32)
+    fptr = np.concatenate([[0], np.cumsum([len(f) for f in fs])]).astype(np.int32)
+    vv = np.ascontiguousarray(np.concatenate(vs) if vs else np.zeros((1, 3)))
+    ff = np.ascontiguousarray(np.concatenate(fs) if fs else np.zeros((1, 3), np.int32))
+    q = np.ascontiguousarray(Q, np.float64).reshape(-1, 3)
+    qn = np.ascontiguousarray(q_nodes, np.int32).reshape(-1)
+    if len(qn) != len(q) or len(exempt) != len(meshes):
+        raise ValueError("hook_collision_prox_exempt: one node per query, one exempt list (or None) per mesh")
+    lists = [np.asarray([] if e is None else e, np.int32).reshape(-1) for e in exempt]
+    eptr = np.concatenate([[0], np.cumsum([len(e) for e in lists])]).astype(np.int32)
+    enodes = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, np.int32)]), np.int32)
+    pp = None
+    if poses is not None:
+        pp = np.full((max(len(meshes), 1), 12), np.nan)
+        for m, p in enumerate(poses):
+            if p is not None:
+                pp[m] = _pose_arg(p)
+    out = np.zeros_like(q)
+    _chk(lib().aa_test_collision_prox_exempt(ctx.h, _dp(rows), C.c_int(len(obstacles)), _dp(vv), _ip(vptr), _ip(ff), _ip(fptr),
+                                             C.c_int(len(meshes)), None if pp is None else _dp(pp), _dp(q), _ip(qn),
+                                             C.c_int(q.shape[0]), _ip(eptr), _ip(enodes), _dp(out)))
+    return out
 
 
 def hook_mesh_sdf_deformed(ctx: Context, V, F, V_new, Q, pose=None, timings=False):

@@ -69,6 +69,9 @@ struct MeshObsDev {
     double lo[3], hi[3];
     double R[9], t[3];
     int posed;
+    // Exemption: one byte per node in the solver's internal numbering, non-zero = that node's
+    // collision term skips this mesh as if it were not in the obstacle list (null = no node is exempt)
+    const unsigned char* exempt;
 };
 
 }  // namespace aa

@@ -228,8 +228,32 @@ int aa_elastic_set_mesh_obstacle_vertices(aa_elastic h, int mesh_id, const doubl
 int aa_elastic_get_mesh_obstacle_vertices(aa_elastic h, int mesh_id, double* verts3, int* n_verts) {
     return guarded([&] {
         NEED(h, "null handle");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
         const int n = h->s->mesh_obstacle_vertices(mesh_id, verts3);
         if (n_verts) *n_verts = n;
+    });
+}
+
+int aa_elastic_bind_mesh_obstacle(aa_elastic h, int mesh_id, const int* nodes, int n_verts) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
+        h->s->bind_mesh_obstacle(mesh_id, nodes, n_verts);
+    });
+}
+
+int aa_elastic_mesh_obstacle_status(aa_elastic h, int mesh_id, int* bound, int* refits, int* skipped, int* last_cause) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        h->s->mesh_obstacle_status(mesh_id, bound, refits, skipped, last_cause);
+    });
+}
+
+int aa_elastic_set_mesh_obstacle_exempt(aa_elastic h, int mesh_id, const int* nodes, int n) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
+        h->s->set_mesh_obstacle_exempt(mesh_id, nodes, n);
     });
 }
 
@@ -687,6 +711,70 @@ double median5_ms(hipStream_t s, F&& f) {
 }
 }  // namespace
 
+extern "C" int aa_test_bound_refit(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
+                                  const double* x3, int n_nodes_x, const int* nodes, int device, void* nodes_bytes,
+                                  double* tris9, double* pn21, int* orig, double* lohi6, int* n_nodes, int* status2,
+                                  double* vol6, double* ms, const double* x3_first) {
+    auto give = [&](const aa::MeshObstacleHost& M) {
+        if (nodes_bytes) std::memcpy(nodes_bytes, M.nodes.data(), sizeof(aa::BvhNode) * M.nodes.size());
+        if (tris9) std::memcpy(tris9, M.tris.data(), sizeof(aa::BvhTri) * M.tris.size());
+        if (pn21) std::copy(M.pn.begin(), M.pn.end(), pn21);
+        if (orig) std::copy(M.orig.begin(), M.orig.end(), orig);
+        if (lohi6) for (int d = 0; d < 3; ++d) { lohi6[d] = M.lo[d]; lohi6[3 + d] = M.hi[d]; }
+        if (n_nodes) *n_nodes = (int)M.nodes.size();
+    };
+    auto check_args = [&] {
+        NEED(x3 && nodes && n_nodes_x > 0, "aa_test_bound_refit: null argument");
+        for (int i = 0; i < n_verts; ++i)
+            NEED(nodes[i] >= 0 && nodes[i] < n_nodes_x, "aa_test_bound_refit: node index out of range");
+    };
+    if (!device)
+        return guarded([&] {
+            aa::MeshObstacleHost M = aa::prepare_mesh_obstacle(verts3, n_verts, tris3, n_tris);
+            check_args();
+            const aa::MeshRefitTables T = aa::make_refit_tables(M, n_verts, tris3, n_tris);
+            double v6 = 0;
+            if (x3_first) aa::bound_refit_host(M, T, x3_first, nodes, &v6);   // an earlier step's refit, taken or refused
+            const int cause = aa::bound_refit_host(M, T, x3, nodes, &v6);
+            if (status2) { status2[0] = cause == aa::BOUND_OK; status2[1] = cause; }
+            if (vol6) *vol6 = v6;
+            give(M);
+        });
+    return with_device_arrays(ctx, [&](hipStream_t s) {
+        aa::MeshObstacleHost M = aa::prepare_mesh_obstacle(verts3, n_verts, tris3, n_tris);
+        check_args();
+        aa::MeshObsBuffers buf;
+        aa::MeshObsDev d = buf.upload(M, s);
+        aa::apply_mesh_pose(d, nullptr);
+        buf.keep_for_refit(M, verts3, n_verts, tris3, n_tris, s);
+        buf.rf.bind(buf.tables, nodes, verts3, s);   // the caller's numbering is the internal one here
+        aa::DevBuf<aa::MeshObsDev> row;
+        row.upload(&d, 1, s);
+        aa::DevBuf<aa::MeshBoundStatus> st(1);
+        st.zero(s);
+        aa::DevBuf<double> xs, xs_first;
+        if (x3_first) {   // an earlier step's refit, taken or refused
+            xs_first.upload(x3_first, 3 * (size_t)n_nodes_x, s);
+            buf.rf.bound_refit(xs_first.p, row.p, st.p, buf.nodes.p, (int)buf.nodes.n, buf.tris.p, buf.pn.p, s);
+        }
+        xs.upload(x3, 3 * (size_t)n_nodes_x, s);
+        buf.rf.bound_refit(xs.p, row.p, st.p, buf.nodes.p, (int)buf.nodes.n, buf.tris.p, buf.pn.p, s);
+        aa::MeshBoundStatus hs;
+        AA_HIP(hipMemcpyAsync(M.nodes.data(), buf.nodes.p, buf.nodes.bytes(), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(M.tris.data(), buf.tris.p, buf.tris.bytes(), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(M.pn.data(), buf.pn.p, buf.pn.bytes(), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(M.orig.data(), buf.orig.p, buf.orig.bytes(), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(&d, row.p, sizeof(d), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipMemcpyAsync(&hs, st.p, sizeof(hs), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipStreamSynchronize(s));
+        for (int k = 0; k < 3; ++k) { M.lo[k] = d.lo[k]; M.hi[k] = d.hi[k]; }
+        if (status2) { status2[0] = hs.skip ? 0 : 1; status2[1] = hs.cause; }
+        if (vol6) *vol6 = hs.vol6;
+        give(M);
+        if (ms) *ms = median5_ms(s, [&] { buf.rf.bound_refit(xs.p, row.p, st.p, buf.nodes.p, (int)buf.nodes.n, buf.tris.p, buf.pn.p, s); });
+    });
+}
+
 extern "C" int aa_test_mesh_sdf_deformed(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
                                         const double* new_verts3, const double* pose12, const double* q3, int n,
                                         double* closest3, double* dx, int* tri, double* ms4) {
@@ -743,7 +831,30 @@ extern "C" int aa_test_collision_prox_posed(aa_ctx ctx, const double* obs_rows, 
                                            const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr,
                                            int n_meshes, const double* mesh_poses, const double* q3, int n,
                                            double* out3) {
+    return aa_test_collision_prox_exempt(ctx, obs_rows, n_obs, mesh_verts3, mesh_vert_ptr, mesh_tris3, mesh_tri_ptr, n_meshes,
+                                         mesh_poses, q3, nullptr, n, nullptr, nullptr, out3);
+}
+
+extern "C" int aa_test_collision_prox_exempt(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
+                                            const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr,
+                                            int n_meshes, const double* mesh_poses, const double* q3, const int* q_node,
+                                            int n, const int* exempt_ptr, const int* exempt_nodes, double* out3) {
     return with_device_arrays(ctx, [&](hipStream_t s) {
+        // q_node null: the form without nodes (aa_test_collision_prox_posed), no exemption
+        NEED(!q_node || (exempt_ptr && (exempt_nodes || exempt_ptr[std::max(n_meshes, 0)] == 0)), "aa_test_collision_prox_exempt: null exempt lists");
+        int n_ids = 1;
+        if (q_node) {
+            for (int e = 0; e < n; ++e) {
+                NEED(q_node[e] >= 0, "aa_test_collision_prox_exempt: negative node id");
+                n_ids = std::max(n_ids, q_node[e] + 1);
+            }
+            for (int m = 0; m < n_meshes; ++m) NEED(exempt_ptr[m + 1] >= exempt_ptr[m], "aa_test_collision_prox_exempt: bad exempt_ptr");
+            for (int j = 0; j < exempt_ptr[n_meshes]; ++j) {
+                NEED(exempt_nodes[j] >= 0, "aa_test_collision_prox_exempt: negative node id");
+                n_ids = std::max(n_ids, exempt_nodes[j] + 1);
+            }
+        }
+        std::vector<std::unique_ptr<aa::DevBuf<unsigned char>>> ebufs;
         NEED(q3 && out3 && n >= 0 && n_obs >= 0 && n_obs <= aa::kMaxObstacles && (obs_rows || n_obs == 0),
              "aa_test_collision_prox: bad argument");
         NEED(n_meshes >= 0 && n_meshes <= aa::kMaxMeshObstacles, "aa_test_collision_prox: too many mesh obstacles");
@@ -760,6 +871,14 @@ extern "C" int aa_test_collision_prox_posed(aa_ctx ctx, const double* obs_rows, 
             if (pose && std::all_of(pose, pose + 12, [](double v) { return std::isnan(v); })) pose = nullptr;   // this mesh unposed
             if (pose) aa::validate_mesh_pose(pose, "aa_test_collision_prox_posed: ");
             aa::apply_mesh_pose(table[m], pose);
+            if (q_node && exempt_ptr[m + 1] > exempt_ptr[m]) {
+                std::vector<unsigned char> bytes((size_t)n_ids, 0);
+                for (int j = exempt_ptr[m]; j < exempt_ptr[m + 1]; ++j) bytes[exempt_nodes[j]] = 1;
+                ebufs.push_back(std::make_unique<aa::DevBuf<unsigned char>>());
+                ebufs.back()->upload(bytes, s);
+                AA_HIP(hipStreamSynchronize(s));
+                table[m].exempt = ebufs.back()->p;
+            }
         }
         std::vector<double> h(1 + (size_t)aa::kObsStride * n_obs, 0.0);
         h[0] = n_obs;
@@ -775,7 +894,13 @@ extern "C" int aa_test_collision_prox_posed(aa_ctx ctx, const double* obs_rows, 
         aa::DevBuf<double> dobs, dq, dout((size_t)3 * std::max(n, 1));
         dobs.upload(h, s);
         dq.upload(q3, (size_t)3 * n, s);
-        aa::launch_test_collision_prox(dobs.p, dtab.p, dq.p, n, dout.p, s);
+        aa::DevBuf<int> dnode;
+        if (q_node) {
+            dnode.upload(q_node, (size_t)n, s);
+            aa::launch_test_collision_prox_exempt(dobs.p, dtab.p, dq.p, dnode.p, n, dout.p, s);
+        } else {
+            aa::launch_test_collision_prox(dobs.p, dtab.p, dq.p, n, dout.p, s);
+        }
         AA_HIP(hipMemcpyAsync(out3, dout.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
         AA_HIP(hipStreamSynchronize(s));
     });

@@ -278,6 +278,14 @@ __device__ inline bool mesh_signed_distance(const MeshObsDev& mo, const double* 
     return true;
 }
 __device__ __forceinline__ const MeshObsDev* mesh_table_of(const MeshObsDev* t) { return t; }
+// Exemption: the pack of the solver's mesh-aware form is (table, the element's node in the internal
+// numbering); a node marked in a row's byte array skips that row as if it were not in the list. The
+// form without a node (the table alone) has no exemption and the code it always had.
+__device__ __forceinline__ const MeshObsDev* mesh_table_of(const MeshObsDev* t, int) { return t; }
+__device__ __forceinline__ bool mesh_exempts(const MeshObsDev&, const MeshObsDev*) { return false; }
+__device__ __forceinline__ bool mesh_exempts(const MeshObsDev& mo, const MeshObsDev*, int node) {
+    return mo.exempt && mo.exempt[node];
+}
 
 // (1/w) * ((w x + u) - c) of an identity-reduction row, without FMA contraction (c = -w x_pin for
 // a pinned node, whose x enters through c: the same sum)
@@ -297,7 +305,8 @@ __device__ inline void collision_candidate(const double* x, const double* u, dou
 // Mesh-aware form: a trailing mesh table (the collision group's parameter pack, as GroupVar is
 // the per-element materials') adds the OBS_MESH rows, o[1] = the mesh's row in the table. An
 // inside hit replaces the running (dx, point) unconditionally -- PassiveMesh::signed_distance has
-// no `if (dx > p.dx) return;` (PassiveObject.hpp:160-175) -- and a miss leaves it untouched.
+// no `if (dx > p.dx) return;` (PassiveObject.hpp:160-175) -- and a miss leaves it untouched. With
+// the element's node after the table, a row that exempts the node is passed over (mesh_exempts).
 // Without the table the code is the analytic shapes' alone.
 template <class... M>
 __device__ inline void collision_prox(const double* q, const double* obs, double* out, M... meshes) {
@@ -341,6 +350,7 @@ __device__ inline void collision_prox(const double* q, const double* obs, double
         } else if (sizeof...(M) != 0 && type == OBS_MESH) {   // PassiveMesh            :138-178
             if constexpr (sizeof...(M) != 0) {
                 const MeshObsDev& mo = mesh_table_of(meshes...)[(int)o[1]];
+                if (mesh_exempts(mo, meshes...)) continue;   // the running payload stays as it is
                 double c[3];
                 int tri;
                 if (!mesh_signed_distance(mo, q, dx, c, tri)) continue;

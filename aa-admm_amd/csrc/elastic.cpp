@@ -200,6 +200,8 @@ void ElasticSolver::set_mesh_obstacle_pose(int mesh_id, const double* pose12) {
     if (mesh_id < 0 || mesh_id >= (int)meshes_.size())
         throw Error(ERR_ARG, "set_mesh_obstacle_pose: unknown mesh id " + std::to_string(mesh_id) + " (" + std::to_string(meshes_.size()) + " meshes)");
     if (pose12) validate_mesh_pose(pose12, "set_mesh_obstacle_pose: ");
+    if (meshes_[mesh_id]->bound)
+        throw Error(ERR_ARG, "set_mesh_obstacle_pose: mesh " + std::to_string(mesh_id) + " is bound to solver nodes (unbind it first)");
     MeshObsDev& d = mesh_rows_[mesh_id];
     apply_mesh_pose(d, pose12);
     AA_HIP(hipMemcpyAsync(mesh_dev_.p + mesh_id, &d, sizeof(d), hipMemcpyHostToDevice, s()));
@@ -222,6 +224,7 @@ void ElasticSolver::set_mesh_obstacle_vertices(int mesh_id, const double* V3) {
     if (mesh_id < 0 || mesh_id >= (int)meshes_.size())
         throw Error(ERR_ARG, who + "unknown mesh id " + std::to_string(mesh_id) + " (" + std::to_string(meshes_.size()) + " meshes)");
     MeshObsBuffers& mo = *meshes_[mesh_id];
+    if (mo.bound) throw Error(ERR_ARG, who + "mesh " + std::to_string(mesh_id) + " is bound to solver nodes (unbind it first)");
     double lo[3], hi[3];
     validate_mesh_refit(mo.tables, V3, who, lo, hi);   // throws before anything is touched
     MeshObsDev& d = mesh_rows_[mesh_id];
@@ -235,9 +238,105 @@ void ElasticSolver::set_mesh_obstacle_vertices(int mesh_id, const double* V3) {
 int ElasticSolver::mesh_obstacle_vertices(int mesh_id, double* V3) const {
     if (mesh_id < 0 || mesh_id >= (int)meshes_.size())
         throw Error(ERR_ARG, "get_mesh_obstacle_vertices: unknown mesh id " + std::to_string(mesh_id) + " (" + std::to_string(meshes_.size()) + " meshes)");
-    const std::vector<double>& v = meshes_[mesh_id]->verts;
-    if (V3) std::copy(v.begin(), v.end(), V3);
+    const MeshObsBuffers& mo = *meshes_[mesh_id];
+    const std::vector<double>& v = mo.verts;
+    if (V3 && mo.bound && initialized_)   // a bound mesh's vertices in force live on the device
+        AA_HIP(hipMemcpy(V3, mo.rf.verts.p, sizeof(double) * v.size(), hipMemcpyDeviceToHost));
+    else if (V3) std::copy(v.begin(), v.end(), V3);
     return (int)v.size() / 3;
+}
+
+MeshObsBuffers& ElasticSolver::mesh_at(int mesh_id, const std::string& who) const {
+    if (mesh_id < 0 || mesh_id >= (int)meshes_.size())
+        throw Error(ERR_ARG, who + "unknown mesh id " + std::to_string(mesh_id) + " (" + std::to_string(meshes_.size()) + " meshes)");
+    return *meshes_[mesh_id];
+}
+
+// Bound obstacles. The binding is kept in the caller's numbering and taken through node2int_ when
+// the numbering exists (here after initialize, else at initialize).
+void ElasticSolver::bind_mesh_obstacle(int mesh_id, const int* nodes, int n_verts) {
+    const std::string who = "bind_mesh_obstacle: ";
+    MeshObsBuffers& mo = mesh_at(mesh_id, who);
+    if (!nodes) {   // unbind: the shape last in force stays
+        if (mo.bound && initialized_) refresh_bound_mesh(mesh_id);
+        mo.bound = false;
+        mo.bound_nodes.clear();
+        return;
+    }
+    const int nv = (int)mo.verts.size() / 3;
+    if (n_verts != nv)
+        throw Error(ERR_ARG, who + std::to_string(n_verts) + " nodes given, mesh " + std::to_string(mesh_id) + " has " + std::to_string(nv) + " vertices");
+    for (int i = 0; i < nv; ++i)
+        if (nodes[i] < 0 || nodes[i] >= num_nodes())
+            throw Error(ERR_ARG, who + "vertex " + std::to_string(i) + " names node " + std::to_string(nodes[i]) + ", out of range (" + std::to_string(num_nodes()) + " nodes)");
+    if (mesh_rows_[mesh_id].posed)
+        throw Error(ERR_ARG, who + "mesh " + std::to_string(mesh_id) + " has a pose (a bound mesh takes its vertices from the solver's nodes; unpose it first)");
+    if (comm_ && comm_->size() > 1)
+        throw Error(ERR_ARG, who + "the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (a rank holds only its part of the nodes; bound obstacles need one rank)");
+    if (mo.bound && initialized_) refresh_bound_mesh(mesh_id);
+    mo.bound_nodes.assign(nodes, nodes + nv);
+    mo.bound = true;
+    h_mesh_status_[mesh_id] = MeshBoundStatus{};
+    AA_HIP(hipMemsetAsync(mesh_status_.p + mesh_id, 0, sizeof(MeshBoundStatus), s()));
+    AA_HIP(hipStreamSynchronize(s()));
+    if (initialized_) upload_mesh_binding(mesh_id);
+}
+
+void ElasticSolver::upload_mesh_binding(int mesh_id) {
+    MeshObsBuffers& mo = *meshes_[mesh_id];
+    std::vector<int> q(mo.bound_nodes.size());
+    for (size_t i = 0; i < q.size(); ++i) q[i] = node2int_[mo.bound_nodes[i]];
+    mo.rf.bind(mo.tables, q.data(), mo.verts.data(), s());
+}
+
+// After device-side refits the host's copies are stale: the row's root box (a later setter writes
+// the row whole and must not put an old box back) and the vertices in force.
+void ElasticSolver::refresh_bound_mesh(int mesh_id) {
+    MeshObsBuffers& mo = *meshes_[mesh_id];
+    MeshObsDev d;
+    AA_HIP(hipStreamSynchronize(s()));
+    AA_HIP(hipMemcpy(&d, mesh_dev_.p + mesh_id, sizeof(d), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; ++k) { mesh_rows_[mesh_id].lo[k] = d.lo[k]; mesh_rows_[mesh_id].hi[k] = d.hi[k]; }
+    AA_HIP(hipMemcpy(mo.verts.data(), mo.rf.verts.p, sizeof(double) * mo.verts.size(), hipMemcpyDeviceToHost));
+}
+
+void ElasticSolver::mesh_obstacle_status(int mesh_id, int* bound, int* refits, int* skipped, int* last_cause) const {
+    const MeshObsBuffers& mo = mesh_at(mesh_id, "mesh_obstacle_status: ");
+    const MeshBoundStatus& st = h_mesh_status_[mesh_id];
+    if (bound) *bound = mo.bound ? 1 : 0;
+    if (refits) *refits = st.refits;
+    if (skipped) *skipped = st.skipped;
+    if (last_cause) *last_cause = st.last_cause;
+}
+
+void ElasticSolver::set_mesh_obstacle_exempt(int mesh_id, const int* nodes, int n) {
+    const std::string who = "set_mesh_obstacle_exempt: ";
+    MeshObsBuffers& mo = mesh_at(mesh_id, who);
+    if (n < 0 || (n > 0 && !nodes)) throw Error(ERR_ARG, who + "null or negative-length node list");
+    for (int i = 0; i < n; ++i)
+        if (nodes[i] < 0 || nodes[i] >= num_nodes())
+            throw Error(ERR_ARG, who + "entry " + std::to_string(i) + " names node " + std::to_string(nodes[i]) + ", out of range (" + std::to_string(num_nodes()) + " nodes)");
+    mo.exempt_nodes.assign(nodes, nodes + n);
+    if (initialized_) upload_mesh_exempt(mesh_id);
+}
+
+// The byte array over the internal numbering and the row's pointer to it. Only that field of the
+// device row is written: a bound mesh's root box is the device's own.
+void ElasticSolver::upload_mesh_exempt(int mesh_id) {
+    MeshObsBuffers& mo = *meshes_[mesh_id];
+    MeshObsDev& d = mesh_rows_[mesh_id];
+    if (mo.exempt_nodes.empty()) {
+        d.exempt = nullptr;
+    } else {
+        std::vector<unsigned char> h((size_t)n_, 0);
+        for (int v : mo.exempt_nodes) h[node2int_[v]] = 1;
+        mo.exempt.upload(h, s());
+        AA_HIP(hipStreamSynchronize(s()));   // h is a temporary
+        d.exempt = mo.exempt.p;
+    }
+    AA_HIP(hipMemcpyAsync(reinterpret_cast<char*>(mesh_dev_.p + mesh_id) + offsetof(MeshObsDev, exempt), &d.exempt,
+                          sizeof(d.exempt), hipMemcpyHostToDevice, s()));
+    AA_HIP(hipStreamSynchronize(s()));
 }
 
 // PassiveMesh: validated and prepared on the host (mesh_obstacle.hpp), uploaded here, and entered
@@ -253,7 +352,12 @@ int ElasticSolver::add_mesh_obstacle(const double* V3, int nv, const int* F3, in
     MeshObsDev d = mo->upload(M, s());
     mo->keep_for_refit(M, V3, nv, F3, nf, s());
     apply_mesh_pose(d, nullptr);
-    if (!mesh_dev_.p) mesh_dev_.alloc(kMaxMeshObstacles);
+    if (!mesh_dev_.p) {
+        mesh_dev_.alloc(kMaxMeshObstacles);
+        mesh_status_.alloc(kMaxMeshObstacles);
+        mesh_status_.zero(s());
+        h_mesh_status_.assign(kMaxMeshObstacles, MeshBoundStatus{});
+    }
     const int row = (int)meshes_.size();
     AA_HIP(hipMemcpyAsync(mesh_dev_.p + row, &d, sizeof(d), hipMemcpyHostToDevice, s()));
     AA_HIP(hipStreamSynchronize(s()));
@@ -392,6 +496,8 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     std::fill(v_.begin(), v_.end(), 0.0);
     if (st_.variant == AA_VARIANT_Z && !obstacles_.empty())   // admm_anderson_xzu/src/Solver.cpp:485-489
         throw Error(ERR_ARG, "**Solver::add_obstacle Error: No collisions with LDLT solver");
+    if (comm_ && comm_->size() > 1 && any_bound())
+        throw Error(ERR_ARG, "initialize: a mesh obstacle is bound to solver nodes and the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (bound obstacles need one rank)");
     if (st_.variant == AA_VARIANT_Z && !coll_nodes_.empty())
         throw Error(ERR_ARG, "set_collisions: energy-based collisions exist in the (u,x) variant only (admm_anderson_hard_zxu)");
     // collision terms (Solver.cpp:386-392): after the other terms, one per node in node order;
@@ -787,6 +893,13 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     AA_HIP(hipStreamSynchronize(s()));
     initialized_ = true;
     upload_obstacles();
+    for (int m = 0; m < (int)meshes_.size(); ++m) {   // bindings and exemptions given before the numbering existed
+        if (meshes_[m]->bound) {
+            if (meshes_[m]->rf.cand.p) refresh_bound_mesh(m);   // a later initialize(): the device holds the shape in force
+            upload_mesh_binding(m);
+        }
+        if (!meshes_[m]->exempt_nodes.empty()) upload_mesh_exempt(m);
+    }
     for (auto& w : winds_) build_wind(*w);
     pins_dirty_ = true;
     rt_ = aa_runtime{};
@@ -900,6 +1013,13 @@ void ElasticSolver::local_z_all(const double* xfull, const double* u, double* z,
 }
 
 void ElasticSolver::prologue() {
+    // bound mesh obstacles take the shape of the step's start state and hold it for every iteration
+    // of the step (lagged, explicit coupling): gather, check and gated refit, all on the stream
+    for (int m = 0; m < (int)meshes_.size(); ++m) {
+        MeshObsBuffers& mo = *meshes_[m];
+        if (mo.bound)
+            mo.rf.bound_refit(xs_.p, mesh_dev_.p + m, mesh_status_.p + m, mo.nodes.p, (int)mo.nodes.n, mo.tris.p, mo.pn.p, s());
+    }
     upload_pins();
     const bool accel = st_.acceleration_type == 1;
     Ctrl c;
@@ -1231,6 +1351,8 @@ void ElasticSolver::epilogue_enqueue(bool accel) {
 void ElasticSolver::fetch_results() {
     Ctrl c;
     AA_HIP(hipMemcpyAsync(&c, ctrl_.p, sizeof(Ctrl), hipMemcpyDeviceToHost, s()));
+    if (any_bound())   // the bound meshes' refit counts ride along; a skipped refit is no failure
+        AA_HIP(hipMemcpyAsync(h_mesh_status_.data(), mesh_status_.p, sizeof(MeshBoundStatus) * meshes_.size(), hipMemcpyDeviceToHost, s()));
     AA_HIP(hipStreamSynchronize(s()));
     nrec_ = std::min(c.nrec, hist_cap_);
     h_prim_.resize(nrec_); h_comb_.resize(nrec_); h_rej_.resize(nrec_);

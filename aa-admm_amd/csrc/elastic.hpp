@@ -51,6 +51,11 @@ struct MeshObsBuffers {
         verts.assign(V3, V3 + 3 * (size_t)nv);
     }
     void refit(const double* V3, hipStream_t s) { rf.refit(V3, nodes.p, (int)nodes.n, tris.p, pn.p, s); }
+    // Bound obstacles: vertex i follows solver node bound_nodes[i] (caller's numbering). Exemption:
+    // the caller's list and its byte array over the internal numbering (allocated at first use).
+    bool bound = false;
+    std::vector<int> bound_nodes, exempt_nodes;
+    DevBuf<unsigned char> exempt;
 };
 
 class ElasticSolver {
@@ -81,6 +86,15 @@ public:
     // box rewritten; no buffer moves, so the graph stays. A refused call changes nothing.
     void set_mesh_obstacle_vertices(int mesh_id, const double* verts3);
     int mesh_obstacle_vertices(int mesh_id, double* verts3) const;   // returns the vertex count
+    // Bound obstacles: vertex i of the mesh follows solver node nodes[i] (null = unbind, the shape
+    // last in force stays). From then on every step() starts by gathering the vertices from the
+    // step's start state on the device, checking them there (check_bound_refit) and, gated on the
+    // outcome, refitting; the obstacle holds that shape for all iterations of the step. Nothing is
+    // copied to or from the host and nothing waited for; the prologue is outside the graph.
+    void bind_mesh_obstacle(int mesh_id, const int* nodes, int n_verts);
+    void mesh_obstacle_status(int mesh_id, int* bound, int* refits, int* skipped, int* last_cause) const;
+    // Exemption: the collision terms of the listed nodes skip this mesh (replaces the earlier list)
+    void set_mesh_obstacle_exempt(int mesh_id, const int* nodes, int n);
     int num_obstacles() const { return (int)obstacles_.size(); }
     void set_obstacle(int index, int type, const double* params);
     // WindForce (ExplicitForce.hpp:39-47) on the given triangles; returns its id
@@ -154,6 +168,15 @@ private:
     std::vector<std::unique_ptr<MeshObsBuffers>> meshes_;
     DevBuf<MeshObsDev> mesh_dev_;
     std::vector<MeshObsDev> mesh_rows_;   // the table's rows as last written
+    // bound meshes: the device status words (one per row; the gate of that mesh's refit kernels)
+    // and their host copies, fetched with the control block
+    DevBuf<MeshBoundStatus> mesh_status_;
+    std::vector<MeshBoundStatus> h_mesh_status_;
+    MeshObsBuffers& mesh_at(int mesh_id, const std::string& who) const;
+    void upload_mesh_binding(int mesh_id);
+    void upload_mesh_exempt(int mesh_id);
+    void refresh_bound_mesh(int mesh_id);   // host row lo / hi and host vertices from the device
+    bool any_bound() const { for (auto& m : meshes_) if (m->bound) return true; return false; }
     const MeshObsDev* mesh_table(const GroupDev& d) const { return d.kind == 2 && !meshes_.empty() ? mesh_dev_.p : nullptr; }
     void build_wind(Wind& w);
     std::vector<int> pin_order_;

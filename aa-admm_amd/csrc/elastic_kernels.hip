@@ -254,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
             // row (EnergyTerm.hpp:166-178: z = W^-1 (W x + u - c), W^-1 stored as 1/w): the
             // contact decision is discrete, so the candidate is rounded like the reference's
             if (variant == 1) dev::collision_candidate(F, uu, w, vin);
-            if constexpr (VAR) dev::collision_prox(vin, g.obs, zz, gvp...);   // the pack is the mesh table
+            if constexpr (VAR) dev::collision_prox(vin, g.obs, zz, gvp..., g.idx[e]);   // the pack is the mesh table; + the node
             else dev::collision_prox(vin, g.obs, zz);
         } else if constexpr (NV == 3) {
             if constexpr (VAR) dev::tri_prox(vin, zz, variant, var_of(gvp...).lmin[e], var_of(gvp...).lmax[e]);
@@ -1798,6 +1798,20 @@ __global__ __launch_bounds__(kBlock) void k_test_collision_prox(const double* __
     for (int i = 0; i < 3; ++i) out[3 * (size_t)e + i] = z[i];
 }
 
+// aa_test_collision_prox_exempt: the solver's form, each query with the node its element would have
+__global__ __launch_bounds__(kBlock) void k_test_collision_prox_exempt(const double* __restrict__ obs,
+                                                                       const MeshObsDev* __restrict__ meshes,
+                                                                       const double* __restrict__ q,
+                                                                       const int* __restrict__ node, int n,
+                                                                       double* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const double p[3] = {q[3 * (size_t)e], q[3 * (size_t)e + 1], q[3 * (size_t)e + 2]};
+    double z[3];
+    dev::collision_prox(p, obs, z, meshes, node[e]);
+    for (int i = 0; i < 3; ++i) out[3 * (size_t)e + i] = z[i];
+}
+
 __global__ __launch_bounds__(kSolveBlock) void k_test_cod(int n, const double* __restrict__ M, const double* __restrict__ b,
                                                           double* __restrict__ x) {
     __shared__ CodLds S;
@@ -2195,6 +2209,13 @@ void launch_test_collision_prox(const double* obs, const MeshObsDev* meshes, con
                                 hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_test_collision_prox, dim3(blocks_for(n)), dim3(kBlock), 0, s, obs, meshes, q, n, out);
+    AA_CHECK_LAUNCH();
+}
+
+void launch_test_collision_prox_exempt(const double* obs, const MeshObsDev* meshes, const double* q, const int* node, int n,
+                                       double* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_test_collision_prox_exempt, dim3(blocks_for(n)), dim3(kBlock), 0, s, obs, meshes, q, node, n, out);
     AA_CHECK_LAUNCH();
 }
 

@@ -205,5 +205,7 @@ void launch_test_mesh_sdf(const MeshObsDev* mesh, const double* q, int n, double
                           hipStream_t s);
 void launch_test_collision_prox(const double* obs, const MeshObsDev* meshes, const double* q, int n, double* out,
                                 hipStream_t s);
+void launch_test_collision_prox_exempt(const double* obs, const MeshObsDev* meshes, const double* q, const int* node, int n,
+                                       double* out, hipStream_t s);
 
 }  // namespace aa

@@ -293,6 +293,68 @@ inline void validate_mesh_refit(const MeshRefitTables& T, const double* V, const
     if (!(vol6 > 0.0)) throw Error(ERR_ARG, who + "the signed volume is not positive: the deformed surface is turned inside out");
 }
 
+// Bound obstacles: a mesh whose vertex i follows solver node nodes[i]. The vertices are gathered on
+// the device from the step's start state, which the host never sees, so the check that decides
+// whether the refit is taken runs there too; check_bound_refit states it and the kernels of
+// mesh_refit.hip reproduce it bit for bit. The causes are validate_mesh_refit's, tested in this
+// order, the lowest-numbered one reported:
+//   BOUND_NONFINITE  a non-finite coordinate among the nv gathered vertices;
+//   BOUND_ZERO_AREA  a triangle with !(dot3(n, n) > 0);
+//   BOUND_VOLUME     !(vol6 > 0), vol6 summed in a fixed shape: the triangles in the caller's order
+//                    are cut into consecutive chunks of kBoundChunk = 256; a chunk's partial is the
+//                    pairwise tree p[i] = p[i] + p[i + w], w = 128, 64, ..., 1 over its terms
+//                    A . (B x C) (absent triangles of the last chunk enter as 0.0), and the partials
+//                    are added in chunk order onto 0.0.
+// lo / hi receive the exact range of the referenced vertices (meaningful when the cause is 0; a
+// tie between -0.0 and +0.0 may resolve either way, which no comparison against the box sees).
+constexpr int kBoundChunk = 256;
+enum BoundCause { BOUND_OK = 0, BOUND_NONFINITE = 1, BOUND_ZERO_AREA = 2, BOUND_VOLUME = 3 };
+
+namespace mesh_detail {
+// one triangle of the check: whether its area vanishes, and its vol6 term A . (B x C)
+AA_HD inline bool bound_tri_term(const double* A, const double* B, const double* C, double& term) {
+    double u[3], w[3], n[3];
+    sub3(B, A, u); sub3(C, A, w); cross3(u, w, n);
+    const bool zero = !(dot3(n, n) > 0.0);
+    cross3(B, C, n);
+    term = dot3(A, n);
+    return zero;
+}
+}  // namespace mesh_detail
+
+// V[i] = x3[nodes[i]], i < nv (the host restatement of the device gather)
+inline void gather_bound_vertices(const double* x3, const int* nodes, int nv, double* V) {
+    for (int i = 0; i < nv; ++i)
+        for (int d = 0; d < 3; ++d) V[3 * (size_t)i + d] = x3[3 * (size_t)nodes[i] + d];
+}
+
+inline int check_bound_refit(const MeshRefitTables& T, const double* V, double* vol6_out, double* lo, double* hi) {
+    using namespace mesh_detail;
+    bool bad = false, zero = false;
+    for (size_t i = 0; i < 3 * (size_t)T.nv; ++i) bad = bad || !std::isfinite(V[i]);
+    const int nf = (int)T.F.size() / 3;
+    for (int d = 0; d < 3; ++d) { lo[d] = DBL_MAX; hi[d] = -DBL_MAX; }
+    double vol6 = 0.0;
+    for (int t0 = 0; t0 < nf; t0 += kBoundChunk) {
+        double p[kBoundChunk];
+        for (int j = 0; j < kBoundChunk; ++j) {
+            p[j] = 0.0;
+            const int t = t0 + j;
+            if (t >= nf) continue;
+            const double *A = V + 3 * (size_t)T.F[3 * (size_t)t], *B = V + 3 * (size_t)T.F[3 * (size_t)t + 1],
+                         *C = V + 3 * (size_t)T.F[3 * (size_t)t + 2];
+            if (bound_tri_term(A, B, C, p[j])) zero = true;
+            for (const double* P : {A, B, C})
+                for (int d = 0; d < 3; ++d) { lo[d] = P[d] < lo[d] ? P[d] : lo[d]; hi[d] = P[d] > hi[d] ? P[d] : hi[d]; }
+        }
+        for (int w = kBoundChunk / 2; w > 0; w >>= 1)
+            for (int j = 0; j < w; ++j) p[j] = p[j] + p[j + w];
+        vol6 = vol6 + p[0];
+    }
+    if (vol6_out) *vol6_out = vol6;
+    return bad ? BOUND_NONFINITE : (zero ? BOUND_ZERO_AREA : (!(vol6 > 0.0) ? BOUND_VOLUME : BOUND_OK));
+}
+
 namespace mesh_detail {
 // unit normal and the three clamped corner angles of a triangle (prepare_mesh_obstacle's formulas)
 AA_HD inline void tri_normal_angles(const double* v9, double* fn, double* ang) {
@@ -367,6 +429,19 @@ inline void refit_mesh_obstacle_host(MeshObstacleHost& M, const MeshRefitTables&
     for (int d = 0; d < 3; ++d) { M.lo[d] = DBL_MAX; M.hi[d] = -DBL_MAX; }
     for (int k = 0; k < nf; ++k)
         for (int c = 0; c < 9; ++c) { M.lo[c % 3] = std::min(M.lo[c % 3], M.tris[k].v[c]); M.hi[c % 3] = std::max(M.hi[c % 3], M.tris[k].v[c]); }
+}
+
+// A bound refit on the host: gather through nodes, check, and refit only when the check passes (a
+// failed check leaves M exactly as it was). Returns the cause.
+inline int bound_refit_host(MeshObstacleHost& M, const MeshRefitTables& T, const double* x3, const int* nodes, double* vol6) {
+    std::vector<double> V(3 * (size_t)T.nv);
+    gather_bound_vertices(x3, nodes, T.nv, V.data());
+    double lo[3], hi[3];
+    const int cause = check_bound_refit(T, V.data(), vol6, lo, hi);
+    if (cause != BOUND_OK) return cause;
+    refit_mesh_obstacle_host(M, T, V.data());
+    for (int d = 0; d < 3; ++d) { M.lo[d] = lo[d]; M.hi[d] = hi[d]; }
+    return cause;
 }
 
 }  // namespace aa

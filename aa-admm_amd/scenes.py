@@ -106,6 +106,12 @@ class Scene:
     # against entry k - 1 and the last entry holds on (capi.run_scene, after the poses). None = the
     # meshes keep their shape.
     mesh_obstacle_vertices: Optional[list] = None
+    # bound mesh obstacles (the obstacle is another simulated body): a list over meshes of (nv,) node
+    # index arrays -- vertex i of the mesh follows node [i] from every step's start state -- or None
+    # for a mesh the caller drives; and, per mesh, the nodes whose collision terms skip that mesh
+    # (a body is exempt from its own surface). None = no mesh is bound / no node is exempt.
+    mesh_obstacle_bindings: Optional[list] = None
+    mesh_obstacle_exempt: Optional[list] = None
     winds: list = dataclasses.field(default_factory=list)
 
     @property
@@ -589,4 +595,62 @@ def cloth_on_breathing_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps
     r = 0.4 * R
     sc.mesh_obstacle_vertices = [[torus_mesh(16, 8, R, r * (1.0 + amplitude * np.sin(np.pi * k / period) ** 2))[0]]
                                  for k in range(1, n_steps + 1)]
+    return sc
+
+
+def kuhn_tet_blocks(cx: int, cy: int, cz: int):
+    """Vertices (n, 3) (tet_blocks' lattice and numbering) and tets (6 cx cy cz, 4) of the Kuhn
+    subdivision: every cube cut into the six tets around its main diagonal, one per order of the
+    axes. Unlike make_tet_blocks' five tets it is conforming -- neighbouring cubes cut their shared
+    face along the same diagonal -- so its boundary faces form a closed surface. Positive volumes."""
+    import itertools
+    g = np.stack(np.meshgrid(np.arange(cx + 1), np.arange(cy + 1), np.arange(cz + 1), indexing="ij"), -1)
+    verts = g.reshape(-1, 3).astype(np.float64)
+    node = lambda p: (p[:, 0] * (cy + 1) + p[:, 1]) * (cz + 1) + p[:, 2]
+    cells = np.stack(np.meshgrid(np.arange(cx), np.arange(cy), np.arange(cz), indexing="ij"), -1).reshape(-1, 3)
+    tets = []
+    for perm in itertools.permutations(range(3)):
+        p = [cells]
+        for a in perm:
+            p.append(p[-1] + np.eye(3, dtype=cells.dtype)[a])
+        t = np.stack([node(q) for q in p], 1)
+        if np.linalg.det(np.eye(3)[list(perm)]) < 0:     # odd order of the axes: mirror image
+            t = t[:, [0, 2, 1, 3]]
+        tets.append(t)
+    return verts, np.stack(tets, 1).reshape(-1, 4).astype(np.int32)
+
+
+def cloth_on_soft_block(nx=12, ny=12, *, cells=(3, 2, 3), cell=0.3, E=5e4, nu=0.3, iters=30, aa_m=6, accel=1, n_steps=8,
+                        drop=0.05) -> Scene:
+    """Demo of the bound mesh obstacle (body-to-body contact, (u,x) variant): a linear-tet block of
+    `cells` cubes of side `cell` (kuhn_tet_blocks: conforming, so its boundary is closed), its bottom-face nodes pinned, soft enough to sag under its own
+    weight over the steps; its boundary faces are mesh obstacle 0, bound to its surface nodes, so
+    the obstacle follows the sagging block. An unpinned nx x ny cloth sheet, a little wider than the
+    block, starts `drop` above the block's top face; its nodes are the collision nodes. Block nodes
+    come first, then the cloth's."""
+    bv, bt = kuhn_tet_blocks(*cells)
+    bv = bv * float(cell)
+    bm = tet_masses(bv, bt, 1522.0)
+    side = 1.2 * cell * max(cells[0], cells[2])
+    cv, ct = tri_blocks(nx, ny)
+    cv = cv * (side / max(nx, ny))
+    cm = tri_masses(cv, ct, 1.0)
+    top = bv[:, 1].max()
+    mid = 0.5 * (bv.max(0) + bv.min(0))
+    cx = np.stack([cv[:, 0] - 0.5 * side + mid[0], np.full(len(cv), top + drop), cv[:, 1] - 0.5 * side + mid[2]], axis=1)
+    nb = len(bv)
+    x = np.concatenate([bv, cx], axis=0)
+    rest = np.concatenate([bv, cv], axis=0)
+    pins = np.nonzero(bv[:, 1] < bv[:, 1].min() + 1e-3 * cell)[0].astype(np.int32)
+    faces = tet_boundary_faces(bv, bt)
+    surf = np.unique(faces).astype(np.int32)           # the block's surface nodes, ascending
+    local = np.full(nb, -1, np.int32)
+    local[surf] = np.arange(len(surf), dtype=np.int32)
+    sc = Scene(x=x, masses=np.concatenate([bm, cm]),
+               groups=[ElementGroup(TET, LINEAR, E, nu, bt), ElementGroup(TRI, LINEAR, 50.0, 0.1, (ct + nb).astype(np.int32), 0.95, 1.05)],
+               pin_idx=pins, pin_pts=bv[pins].copy(), pin_vel=np.zeros((len(pins), 3)), variant=VARIANT_H, iters=iters,
+               aa_m=aa_m, n_steps=n_steps, accel=accel, name="cloth_on_soft_block", rest=rest)
+    sc.mesh_obstacles = [(bv[surf].copy(), local[faces].astype(np.int32))]
+    sc.mesh_obstacle_bindings = [surf]
+    sc.collision_idx = np.arange(nb, nb + len(cx), dtype=np.int32)
     return sc

@@ -213,6 +213,52 @@ int aa_elastic_get_mesh_obstacle_pose(aa_elastic h, int mesh_id, double pose12[1
  * their count (n_verts may be NULL). */
 int aa_elastic_set_mesh_obstacle_vertices(aa_elastic h, int mesh_id, const double* verts3);
 int aa_elastic_get_mesh_obstacle_vertices(aa_elastic h, int mesh_id, double* verts3, int* n_verts);
+/* Bound obstacles: the obstacle is another simulated body. Vertex i of mesh obstacle mesh_id follows
+ * solver node nodes[i] (the caller's numbering; any node, pinned ones included; n_verts = the mesh's
+ * vertex count). nodes = NULL unbinds; the shape last in force stays. May be called before or after
+ * initialize and between steps. From then on every aa_elastic_step begins -- before wind, before
+ * the first local step -- by gathering the mesh's vertices on the device from the step's start
+ * positions and running the refit of aa_elastic_set_mesh_obstacle_vertices on them, on the solver's
+ * stream: no host copy, no wait. That work precedes the captured iteration graph, so binding and
+ * unbinding keep the graph.
+ * Coupling: the obstacle holds its start-of-step shape for every ADMM iteration of that step --
+ * lagged, explicit coupling. It has no velocity and exerts no friction, and it is refitted once per
+ * step, not more often. The BVH is not rebuilt when the shape drifts far from the added one: the
+ * cost growth stated above for the vertex setter applies alike.
+ * Validity is decided on the device, because the host never sees the gathered shape. The causes
+ * are the vertex setter's, tested in this order, the lowest-numbered one reported:
+ *   1  a non-finite gathered coordinate;
+ *   2  a triangle with !(n . n > 0), n = (B - A) x (C - A);
+ *   3  !(vol6 > 0), vol6 = the sum of A . (B x C) in a fixed shape: the triangles in the caller's
+ *      order in consecutive chunks of 256, a chunk's partial the pairwise tree p[i] += p[i + w],
+ *      w = 128 .. 1 (absent triangles of the last chunk count 0), the partials added in chunk order.
+ * When the check fails every refit kernel and the kernel that writes the row's root box exit at
+ * once (gated on a device status word) and the obstacle stays exactly as it was after its last
+ * good refit; aa_elastic_step does not fail. When it passes, the tables are what
+ * aa_elastic_set_mesh_obstacle_vertices writes for the same positions, bit for bit, and the root
+ * box is the exact range of the gathered vertices.
+ * aa_elastic_mesh_obstacle_status (every output optional): whether the mesh is bound, the refits
+ * taken and skipped since binding, and the cause (above; 0 = none) of the last skipped one; the
+ * counts arrive with the step's other results. aa_elastic_get_mesh_obstacle_vertices returns the
+ * vertices in force, after a skipped refit the earlier ones.
+ * AA_ERR_ARG, the message naming the cause: an unknown mesh_id, n_verts not the mesh's vertex
+ * count, a node index out of range, a mesh that has a pose, a solver partitioned over more than one
+ * rank (a rank holds only its part of the nodes: partitioned binding is out of scope).
+ * aa_elastic_set_mesh_obstacle_pose and aa_elastic_set_mesh_obstacle_vertices refuse a bound mesh.
+ * Not provided: self-collision (see the exemption below), partitioned solvers, friction or obstacle
+ * velocity, more than one refit per step, a BVH rebuild on drift, and the z-AA variant, which
+ * refuses collision terms as before. */
+int aa_elastic_bind_mesh_obstacle(aa_elastic h, int mesh_id, const int* nodes, int n_verts);
+int aa_elastic_mesh_obstacle_status(aa_elastic h, int mesh_id, int* bound, int* refits, int* skipped, int* last_cause);
+/* Exemption: the collision terms of the n listed nodes (caller's numbering) skip mesh obstacle
+ * mesh_id as if it were not in the obstacle list -- the running (dx, point) is left untouched and
+ * later obstacles compete as before. The list replaces the earlier one; n = 0 clears it. Any mesh,
+ * bound or not, before or after initialize, between steps; the captured graph is kept (one byte per
+ * node on the device, reached from the mesh's table row). A body whose surface is a bound obstacle
+ * exempts its own nodes, or its interior nodes would be projected out of their own surface.
+ * A node is exempt from a whole mesh, not from its incident triangles only, so self-collision is
+ * not provided. AA_ERR_ARG: an unknown mesh_id, a null list with n > 0, a node out of range. */
+int aa_elastic_set_mesh_obstacle_exempt(aa_elastic h, int mesh_id, const int* nodes, int n);
 /* The number of obstacle rows, analytic and mesh, in the shared insertion order. */
 int aa_elastic_num_obstacles(aa_elastic h, int* n);
 /* Re-parameterises the analytic obstacle at position `index` of that order (a rising floor, a
@@ -432,7 +478,16 @@ int aa_geom_set_comm(aa_geom h, aa_comm c);
  *     the device to new_verts3. ms4 (optional) receives four times in ms: host preparation plus
  *     upload of the deformed mesh from scratch (wall), the device refit, the signed-distance kernel
  *     on the refitted tree and on a freshly built tree of the same shape (the last three by device
- *     events, the median of 5 runs after a warm-up). */
+ *     events, the median of 5 runs after a warm-up).
+ *   aa_test_bound_refit: the mesh built from verts3 / tris3, its vertices gathered from the n_nodes_x
+ *     positions x3 through nodes (vertex i = x3[nodes[i]]), then checked and -- if the check passes --
+ *     refitted (aa_elastic_bind_mesh_obstacle); x3_first (optional): a bound refit from these
+ *     positions runs before it, as an earlier step's would. device = 0 the host restatement (ctx
+ *     may be NULL), 1 what the kernels wrote. Outputs of aa_test_mesh_refit_tables plus status2 = {taken, cause}
+ *     and vol6, the check's chunked sum; ms (optional, device = 1): the device time of gather +
+ *     check + refit by device events, the median of 5 runs after a warm-up.
+ *   aa_test_collision_prox_exempt: aa_test_collision_prox_posed with a node id per query (q_node)
+ *     and per mesh a list of exempt nodes (mesh m: exempt_nodes[exempt_ptr[m]..exempt_ptr[m+1])). */
 int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double* in, int n, double* out, int* iters);
 int aa_test_cod_solve(aa_ctx ctx, int k, const double* M, const double* b, double* theta);
 int aa_test_geom_project(aa_ctx ctx, int type, int k, const double* prm2, const double* in, int n, double* out);
@@ -452,6 +507,14 @@ int aa_test_mesh_refit_tables(aa_ctx ctx, const double* verts3, int n_verts, con
 int aa_test_mesh_sdf_deformed(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
                               const double* new_verts3, const double* pose12, const double* q3, int n,
                               double* closest3, double* dx, int* tri, double* ms4);
+int aa_test_bound_refit(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris, const double* x3,
+                        int n_nodes_x, const int* nodes, int device, void* nodes_bytes, double* tris9, double* pn21,
+                        int* orig, double* lohi6, int* n_nodes, int* status2, double* vol6, double* ms,
+                        const double* x3_first);
+int aa_test_collision_prox_exempt(aa_ctx ctx, const double* obs_rows, int n_obs, const double* mesh_verts3,
+                                  const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr, int n_meshes,
+                                  const double* mesh_poses, const double* q3, const int* q_node, int n,
+                                  const int* exempt_ptr, const int* exempt_nodes, double* out3);
 /* The global step's sparse triangular solve alone (DirectSolver, csrc/direct_solve.hpp), on a
  * caller-given SPD matrix: full-pattern symmetric CSR (ptr, col, val; sorted columns, every
  * diagonal stored) of order n in the caller's ordering, node coordinates xyz3.

@@ -15,6 +15,7 @@
 //   solver.step();                                     // Solver::step; solver.m_x / m_v updated
 //   solver.set_obstacle_pose(mesh, R, t); solver.update_obstacle(floor);   // kinematic obstacles, between steps
 //   solver.set_obstacle_vertices(mesh, new_verts);                         // a mesh that changes shape
+//   solver.bind_obstacle(mesh, surface_nodes); solver.exempt_from_obstacle(mesh, body_nodes);   // body-to-body contact
 //
 // Energy terms are descriptors of the built-in element kinds (batched SoA on the device);
 // user-defined EnergyTerm subclasses with arbitrary prox() are not supported (no host
@@ -314,6 +315,28 @@ public:
         check(aa_elastic_set_mesh_obstacle_vertices(h_, mesh->mesh_id, verts3.data()));
         mesh->verts = verts3;
     }
+    // Bound obstacles (no reference behaviour: add_dynamic_collider / surface_inds are registered
+    // there but never asked; aa_admm.h, aa_elastic_bind_mesh_obstacle): the mesh is the surface of
+    // another simulated body -- vertex i follows node nodes[i] from every step's start state, gathered
+    // and refitted on the device; an empty list unbinds. exempt_from_obstacle: the collision terms of
+    // `nodes` skip the mesh (a body's own nodes; an empty list clears). Before the first
+    // initialize() the device solver has no nodes yet: both are kept and handed over with them.
+    void bind_obstacle(const std::shared_ptr<PassiveMesh>& mesh, const std::vector<int>& nodes) {
+        if (!mesh || mesh->mesh_id < 0 || row_of(mesh.get()) < 0) throw std::runtime_error("bind_obstacle: the mesh was not added to this solver");
+        if (!nodes.empty() && 3 * nodes.size() != mesh->verts.size()) throw std::runtime_error("bind_obstacle: one node per vertex of the mesh");
+        if (!bound_) { pending_.push_back({0, mesh->mesh_id, nodes}); return; }
+        check(aa_elastic_bind_mesh_obstacle(h_, mesh->mesh_id, nodes.empty() ? nullptr : nodes.data(), (int)nodes.size()));
+    }
+    void exempt_from_obstacle(const std::shared_ptr<PassiveMesh>& mesh, const std::vector<int>& nodes) {
+        if (!mesh || mesh->mesh_id < 0 || row_of(mesh.get()) < 0) throw std::runtime_error("exempt_from_obstacle: the mesh was not added to this solver");
+        if (!bound_) { pending_.push_back({1, mesh->mesh_id, nodes}); return; }
+        check(aa_elastic_set_mesh_obstacle_exempt(h_, mesh->mesh_id, nodes.data(), (int)nodes.size()));
+    }
+    // refits taken / skipped since the mesh was bound, and the cause of the last skipped one
+    void obstacle_status(const std::shared_ptr<PassiveMesh>& mesh, int& refits, int& skipped, int& last_cause) const {
+        if (!mesh || mesh->mesh_id < 0) throw std::runtime_error("obstacle_status: the mesh was not added to this solver");
+        check(aa_elastic_mesh_obstacle_status(h_, mesh->mesh_id, nullptr, &refits, &skipped, &last_cause));
+    }
     // ... and the analytic shapes: change obj->params, then call this to re-send them to the row
     // the obstacle was added as
     void update_obstacle(std::shared_ptr<PassiveCollision> obj) {
@@ -356,6 +379,13 @@ public:
             }
             bound_ = true;
             if (!collisions_.empty() && aa_elastic_set_collisions(h_, collisions_.data(), (int)collisions_.size()) != AA_OK) return false;
+            for (auto& p : pending_) {   // bind_obstacle / exempt_from_obstacle calls made before the nodes existed
+                const int rc = p.kind == 0
+                    ? aa_elastic_bind_mesh_obstacle(h_, p.mesh_id, p.nodes.empty() ? nullptr : p.nodes.data(), (int)p.nodes.size())
+                    : aa_elastic_set_mesh_obstacle_exempt(h_, p.mesh_id, p.nodes.data(), (int)p.nodes.size());
+                if (rc != AA_OK) return false;
+            }
+            pending_.clear();
         }
         push_pins();
         aa_settings cs{s.timestep_s, s.verbose, s.admm_iters, s.gravity, s.constraint_w, s.Anderson_m, s.penalty,
@@ -441,6 +471,8 @@ private:
     std::vector<int> pins_, collisions_;
     std::vector<double> pin_pts_;
     std::vector<std::shared_ptr<PassiveCollision>> obstacles_;   // by row of the insertion order
+    struct PendingNodes { int kind, mesh_id; std::vector<int> nodes; };   // kind 0 bind, 1 exempt
+    std::vector<PendingNodes> pending_;
     int row_of(const PassiveCollision* o) const {
         for (size_t k = 0; k < obstacles_.size(); ++k)
             if (obstacles_[k].get() == o) return (int)k;
