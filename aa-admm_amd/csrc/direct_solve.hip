@@ -1,6 +1,5 @@
 // GPU supernodal triangular solves (see direct_solve.hpp).
 #include "direct_solve.hpp"
-#include "solve_plan.hpp"
 
 #include <omp.h>
 
@@ -22,8 +21,6 @@ __device__ __forceinline__ bool solve_gated(const Ctrl* c, int gate_reject) {
     return gate_reject && !c->reject;
 }
 
-using Task = DirectSolver::Task;
-
 // Split-K hand-off inside one launch (MI355X_MICROARCH.md "Valid forms"; the publish recipe of
 // cdna_hip_programming.md Guideline 16): partials are stored write-through (sc1: relaxed
 // agent-scope 8-B atomic stores, so no release / L2 write-back), the storing wave drains
@@ -44,7 +41,7 @@ __device__ __forceinline__ bool arrive_last(int* cnt, int nt, int lane) {
     return (int)prev == nt - 1;
 }
 
-// Factor loads (NT = DirectSolver::nt_): a factor streamed past the Infinity Cache (both sweeps'
+// Factor loads (NT = SolvePlan::nt): a factor streamed past the Infinity Cache (both sweeps'
 // copies > kNtBytes: C3, C4, C5) is read with non-temporal loads -- each entry is read once per
 // sweep by exactly one workgroup (MI355X_MICROARCH.md, nt-weights): C4 two-set solve 753 -> 741 us,
 // C3 1 138 -> 1 207 it/s. A factor that stays resident (C2, ~120 MB working set) keeps plain
@@ -304,7 +301,7 @@ __global__ __launch_bounds__(BLOCK) void k_bwd(const Task* __restrict__ tasks, i
 
 // Backward sweep of the large supernodes (R > kWaveR) as a split-K GEMV: tile = 128 columns
 // (2 per lane, one 16-B load each: rows of G are padded to an even length) x kBwdTileRows rows
-// (4 waves x kBwdTileRows/4 rows; kBwdTileRows = DirectSolver::tile_w_, 128 or 256) of the
+// (4 waves x kBwdTileRows/4 rows; kBwdTileRows = the tile width, 128 or 256) of the
 // row-major G, the tile's slice of [y_P ; -x_B] staged in LDS, one
 // 128 x NR partial per tile; the last tile of a column block to finish sums the block's partials
 // in tile order (deterministic; hand-off protocol above). Gives (columns/128) x (rows/kBwdTileRows)
@@ -325,8 +322,6 @@ __global__ __launch_bounds__(BLOCK) void k_bwd(const Task* __restrict__ tasks, i
 #ifndef AA_TILE_DEPTH
 #define AA_TILE_DEPTH 2
 #endif
-using BTile = DirectSolver::BTile;
-using BRed = DirectSolver::BRed;
 template <int NR, int CH, int kBwdTileRows>
 __global__ __launch_bounds__(256, AA_TILE_MINW) void k_bwd_tile(const BTile* __restrict__ tiles, int first, const double* __restrict__ Gr,
                                                   const int* __restrict__ bnd, const double* __restrict__ Y,
@@ -423,8 +418,6 @@ __global__ __launch_bounds__(256, AA_TILE_MINW) void k_bwd_tile(const BTile* __r
 // assembled front f_P staged in LDS, one 64 x NR partial per tile; the last tile of a row block
 // to finish sums its partials in tile order and writes y_P (rows < p) or the update vector
 // u = f_B - M f_P.
-using FTile = DirectSolver::FTile;
-using FRed = DirectSolver::FRed;
 template <int NR, int CH, int kFwdTileCols>
 __global__ __launch_bounds__(256, AA_TILE_MINW) void k_fwd_tile(const FTile* __restrict__ tiles, int first, const double* __restrict__ Gc,
                                                   const long long* __restrict__ ell, const double* __restrict__ B0,
@@ -523,12 +516,12 @@ __global__ __launch_bounds__(256, AA_TILE_MINW) void k_fwd_tile(const FTile* __r
 
 // Packed split-K tiles (the default): the same tiles, partials and reductions as k_fwd_tile /
 // k_bwd_tile -- so the same sums in the same order, bit-identical -- but the factor entries of a
-// tile come from its own contiguous block of Gt (DirectSolver::build packs them), laid out in the
+// tile come from its own contiguous block of Gt (DirectSolver::upload_factor packs them), laid out in the
 // order the tile's waves consume them: each wave streams a sequential run of 1-KB rows (64 lanes
 // x 16 B, two columns or two rows' entries per lane). The column-major / row-major copies put a
 // tile's 64 x 256 entries in 256 pieces of 512 B (or 1 KB) at strides of the supernode's height,
 // spread over several MB: a DRAM-page and TLB pattern a contiguous stream avoids.
-// Streamed levels (DirectSolver::Stream): the workgroup's tile is the next ticket of the launch's
+// Streamed levels (Stream, solve_plan.hpp): the workgroup's tile is the next ticket of the launch's
 // queue (level order), not blockIdx -- so every tile a workgroup waits for was taken earlier by a
 // workgroup that is running or done, whatever the dispatch order (no deadlock).
 __device__ __forceinline__ int stream_ticket(const int* __restrict__ order, int first, int* sync, int head) {
@@ -915,10 +908,6 @@ __global__ __launch_bounds__(256) void k_top_scatter(const Task* __restrict__ to
     st_ext<NR>(X0, X1, (size_t)(t.beg + q), a);
 }
 
-using SubNode = DirectSolver::SubNode;
-using SubLevel = DirectSolver::SubLevel;
-using SubTree = DirectSolver::SubTree;
-
 // forward sweep of a whole bottom subtree (one workgroup), its levels bottom-up
 template <int BLOCK, int NR, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_fwd_sub(const SubTree* __restrict__ trees, const SubLevel* __restrict__ lvls,
@@ -1001,10 +990,6 @@ __global__ __launch_bounds__(BLOCK) void k_fwd_sub(const SubTree* __restrict__ t
 // column), consecutive threads on consecutive columns of one row -> coalesced), partials in
 // LDS, then one item per column sums its segments in order: short loops instead of one thread
 // walking all R rows of a column.
-#ifndef AA_SUB_SEG
-#define AA_SUB_SEG 64
-#endif
-constexpr int kSubSegRows = AA_SUB_SEG;
 __device__ __forceinline__ int sub_seg_off(int seg, int p) {   // partial slots before segment seg
     int o = 0;
     for (int q = 0; q < seg; ++q) o += min(p, (q + 1) * kSubSegRows);
@@ -1132,64 +1117,52 @@ __global__ void k_gr_to_gc(const TrTile* __restrict__ tiles, const double* __res
     }
 }
 
-}  // namespace
+// the packed-tile kernel for a width and a load flavour (STREAM: a streamed run's)
+template <int NR, bool STREAM>
+auto fwd_ptile(int w, bool nt) {
+    return w == 256 ? (nt ? k_fwd_ptile<NR, AA_FWD_CH, 256, AA_TILE_DEPTH, STREAM, true> : k_fwd_ptile<NR, AA_FWD_CH, 256, AA_TILE_DEPTH, STREAM, false>)
+         : w == 128 ? (nt ? k_fwd_ptile<NR, AA_FWD_CH, 128, AA_TILE_DEPTH, STREAM, true> : k_fwd_ptile<NR, AA_FWD_CH, 128, AA_TILE_DEPTH, STREAM, false>)
+                    : (nt ? k_fwd_ptile<NR, AA_FWD_CH, 64, AA_TILE_DEPTH, STREAM, true> : k_fwd_ptile<NR, AA_FWD_CH, 64, AA_TILE_DEPTH, STREAM, false>);
+}
+template <int NR, bool STREAM>
+auto bwd_ptile(int w, bool nt) {
+    return w == 256 ? (nt ? k_bwd_ptile<NR, AA_BWD_CH, 256, AA_TILE_DEPTH, STREAM, true> : k_bwd_ptile<NR, AA_BWD_CH, 256, AA_TILE_DEPTH, STREAM, false>)
+         : w == 128 ? (nt ? k_bwd_ptile<NR, AA_BWD_CH, 128, AA_TILE_DEPTH, STREAM, true> : k_bwd_ptile<NR, AA_BWD_CH, 128, AA_TILE_DEPTH, STREAM, false>)
+                    : (nt ? k_bwd_ptile<NR, AA_BWD_CH, 64, AA_TILE_DEPTH, STREAM, true> : k_bwd_ptile<NR, AA_BWD_CH, 64, AA_TILE_DEPTH, STREAM, false>);
+}
 
-void DirectSolver::build(const SupernodalFactor& F, hipStream_t s, const std::vector<int>* node_part, int my_part,
-                         int top_beg, Comm* comm, int max_sets, bool wide, int wave_p, int wave_r) {
-    n_ = F.n;
-    max_sets_ = max_sets >= 2 ? 2 : 1;
-    // LDS scale the layout (fused-subtree cut, tile width) is planned for: the two-set budget
-    // whenever `wide`, so a one-set solver built wide sums every column in the same order as a
-    // two-set one (bit-identical AA_Z_PIPELINE=0 / 1)
-    const int KS = (wide || max_sets_ >= 2) ? 2 : 1;
-    nn_ = F.n_nodes;
-    comm_ = (node_part && comm && comm->size() > 1) ? comm : nullptr;
-    top_beg_ = comm_ ? top_beg : n_;
-    // partitioned: this GPU holds the supernodes of its own part and the shared top only
-    std::vector<char> inc(nn_, 1);
-    if (comm_)
-        for (int sn = 0; sn < nn_; ++sn) inc[sn] = (*node_part)[sn] == my_part || (*node_part)[sn] == -1;
-    std::vector<int> beg(nn_), p(nn_), nb(nn_), bnd_off(nn_), bnd, pull_off(nn_);
-    std::vector<long long> goff(nn_), uoff(nn_);
-    std::vector<int> ldr(nn_, 0);
-    long long go = 0, uo = 0;
-    double dense = 0, offd = 0, bsum = 0, piv = 0;
-    int rows_total = 0;
-    nnz_L_ = 0;
-    for (int sn = 0; sn < nn_; ++sn) {
-        const int ps = F.end[sn] - F.beg[sn], nbs = (int)F.bnd[sn].size();
-        beg[sn] = F.beg[sn]; p[sn] = ps; nb[sn] = nbs;
-        goff[sn] = go; uoff[sn] = uo;
-        ldr[sn] = ps + (ps & 1);   // row-major rows padded to even length (16-B loads in k_bwd_tile)
-        bnd_off[sn] = (int)bnd.size();
-        pull_off[sn] = rows_total;
-        if (!inc[sn]) continue;
-        bnd.insert(bnd.end(), F.bnd[sn].begin(), F.bnd[sn].end());
-        rows_total += ps + nbs;
-        nnz_L_ += (size_t)ps * (ps + 1) / 2 + (size_t)ps * nbs;
-        go += (long long)(ps + nbs) * (ps + (ps & 1));
-        uo += 3LL * nbs;
-        uo = (uo + 15) / 16 * 16;   // every update vector on 128-B lines of its own (streamed levels)
-        dense += 0.5 * ps * (ps + 1.0);
-        offd += (double)ps * nbs;
-        piv += ps;
-        bsum += nbs;
-    }
-    // G_s = [Linv ; M], M = L_BP Linv: the row-major copy Gr is formed here (every entry written,
-    // so no zero fill of the 1 GB buffer), the column-major copy Gc on the device from it
-    std::unique_ptr<double[]> Gr(new double[std::max<long long>(go, 1)]);
+// opt the thread-per-row kernels in to 160 KiB of dynamic LDS (the default is 64 KiB): every
+// instantiation a solve can launch (3 block sizes x forward / backward, per NR and NT)
+void raise_lds(std::initializer_list<const void*> kernels) {
+    for (const void* k : kernels) AA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+}
+template <int NR, bool NT>
+void raise_sub_lds() {
+    raise_lds({(const void*)k_fwd_sub<256, NR, NT>, (const void*)k_fwd_sub<512, NR, NT>, (const void*)k_fwd_sub<1024, NR, NT>,
+               (const void*)k_bwd_sub<256, NR, NT>, (const void*)k_bwd_sub<512, NR, NT>, (const void*)k_bwd_sub<1024, NR, NT>});
+}
+template <int NR, bool NT>
+void raise_row_lds() {
+    raise_lds({(const void*)k_fwd<64, NR, NT>, (const void*)k_fwd<128, NR, NT>, (const void*)k_fwd<256, NR, NT>,
+               (const void*)k_bwd<64, NR, NT>, (const void*)k_bwd<128, NR, NT>, (const void*)k_bwd<256, NR, NT>});
+}
+
+// G_s = [Linv ; M], M = L_BP Linv, row-major with rows of ldr doubles, every held supernode at its
+// goff: every entry is written, so no zero fill of the (up to 1 GB) buffer
+std::unique_ptr<double[]> form_gr(const SupernodalFactor& F, const SolvePlan& P) {
+    std::unique_ptr<double[]> Gr(new double[std::max<long long>(P.g_doubles, 1)]);
 #pragma omp parallel for schedule(dynamic, 1)
-    for (int sn = 0; sn < nn_; ++sn) {
-        if (!inc[sn]) continue;
-        const int ps = p[sn], nbs = nb[sn], R = ps + nbs, ld = ldr[sn];
-        double* gr = Gr.get() + goff[sn];
+    for (int sn = 0; sn < P.nn; ++sn) {
+        if (!P.inc[sn]) continue;
+        const int ps = P.p[sn], nbs = P.nb[sn], R = ps + nbs, ld = P.ldr[sn];
+        double* gr = Gr.get() + P.goff[sn];
         const std::vector<double>& Li = F.Linv[sn];
         const std::vector<double>& LB = F.LBP[sn];
         for (int r = 0; r < R; ++r)
             for (int c = ps; c < ld; ++c) gr[(size_t)r * ld + c] = 0.0;   // pad column
         for (int r = 0; r < ps; ++r)
             for (int c = 0; c < ps; ++c) gr[(size_t)r * ld + c] = c <= r ? Li[(size_t)r * ps + c] : 0.0;
-        const bool have_m = F.M.size() == (size_t)nn_ && F.M[sn].size() == (size_t)nbs * ps;
+        const bool have_m = F.M.size() == (size_t)P.nn && F.M[sn].size() == (size_t)nbs * ps;
         for (int a = 0; a < nbs; ++a) {
             double* m = gr + (size_t)(ps + a) * ld;
             if (have_m) {   // formed with the factor (dense backend)
@@ -1205,937 +1178,121 @@ void DirectSolver::build(const SupernodalFactor& F, hipStream_t s, const std::ve
             }
         }
     }
-    // children lists and ELL pull lists (front row q of a parent <- child update entries, fixed order)
-    // (partitioned: the children of the top that belong to other GPUs' parts contribute nothing
-    // here -- their update vectors arrive through the all-reduce of the top rows)
-    std::vector<std::vector<int>> kl(nn_);
-    for (int sn = 0; sn < nn_; ++sn) if (F.parent[sn] >= 0 && inc[sn]) kl[F.parent[sn]].push_back(sn);
-    std::vector<std::vector<long long>> pull(rows_total);
-    for (int par = 0; par < nn_; ++par) {
-        const std::vector<int>& pb = F.bnd[par];
-        for (int c : kl[par]) {
-            for (int a = 0; a < nb[c]; ++a) {
-                const int i = F.bnd[c][a];
-                int q;
-                if (i >= F.beg[par] && i < F.end[par]) q = i - F.beg[par];
-                else {
-                    auto it = std::lower_bound(pb.begin(), pb.end(), i);
-                    if (it == pb.end() || *it != i) throw Error(ERR_NUMERIC, "DirectSolver: inconsistent supernode structure");
-                    q = p[par] + (int)(it - pb.begin());
-                }
-                pull[pull_off[par] + q].push_back(uoff[c] + 3LL * a);
-            }
-        }
-    }
-    std::vector<int> ell_w(nn_, 0);
-    std::vector<long long> ell_off(nn_, 0), ell;
-    for (int sn = 0; sn < nn_; ++sn) {
-        const int R = inc[sn] ? p[sn] + nb[sn] : 0;
-        int w = 0;
-        for (int q = 0; q < R; ++q) w = std::max(w, (int)pull[pull_off[sn] + q].size());
-        ell_w[sn] = w;
-        ell_off[sn] = (long long)ell.size();
-        for (int q = 0; q < R; ++q) {
-            const auto& l = pull[pull_off[sn] + q];
-            for (int k = 0; k < w; ++k) ell.push_back(k < (int)l.size() ? l[k] : -1);
-        }
-    }
-    // ---- fused bottom subtrees: the largest cut height H such that at least `min_sub`
-    // subtrees root at height <= H (enough workgroups to fill the chip) and every subtree level
-    // fits the LDS budget; supernodes above H are solved level by level.
-    std::vector<std::vector<int>> kids(nn_);
-    for (int sn = 0; sn < nn_; ++sn) if (F.parent[sn] >= 0 && inc[sn]) kids[F.parent[sn]].push_back(sn);
-    const char* ms = std::getenv("AA_SOLVE_MIN_SUBTREES");
-    const bool stats = std::getenv("AA_SOLVE_STATS") != nullptr;
-    const char* sb = std::getenv("AA_SUB_BLOCK");
-    sub_block_ = sb ? std::atoi(sb) : 1024;
-    // split-K tile width (forward columns / backward rows) per level: the widest of 256 / 128 /
-    // 64 that still gives the level >= min_tiles workgroups (a level of few big supernodes gets
-    // narrow tiles and enough workgroups to keep loads in flight on every CU; wide tiles keep the
-    // partial traffic low where there is parallelism anyway). Structure only: the same for
-    // one- and two-set solves. AA_SOLVE_TILE forces one width, AA_SOLVE_MIN_TILES the target.
-    const char* tw = std::getenv("AA_SOLVE_TILE");
-    const char* mt = std::getenv("AA_SOLVE_MIN_TILES");
-    const int min_tiles = mt ? std::atoi(mt) : 0;   // 0: 256 everywhere (narrower measured slower on C4)
-    const char* wp = std::getenv("AA_SOLVE_WAVEP");
-    const char* wr = std::getenv("AA_SOLVE_WAVER");
-    wave_p_ = wp ? std::atoi(wp) : wave_p;
-    wave_r_ = wr ? std::atoi(wr) : wave_r;
-    // fused subtrees wanted: enough workgroups to fill the chip on one GPU; a partitioned GPU's
-    // share of the tree is P times smaller, and its fused subtrees cost a latency chain per level
-    // whatever their count, so it takes fewer, taller ones (measured)
-    const int min_sub = ms ? std::atoi(ms) : (comm_ ? std::max(32, 256 / comm_->size()) : 256);
-    auto roots_at = [&](int H) {
-        std::vector<int> r;
-        for (int sn = 0; sn < nn_; ++sn)
-            if (inc[sn] && F.height[sn] <= H && (F.parent[sn] < 0 || F.height[F.parent[sn]] > H)) r.push_back(sn);
-        return r;
-    };
-    auto collect = [&](int root) {
-        std::vector<int> out, st{root};
-        while (!st.empty()) { int v = st.back(); st.pop_back(); out.push_back(v); for (int c : kids[v]) st.push_back(c); }
-        return out;
-    };
-    {   // the cut height against the launch's aggregate LDS (solve_plan.hpp; the fused kernels'
-        // LDS attribute is 160 KiB, set below)
-        CutPlanIn pl;
-        pl.parent = &F.parent; pl.height = &F.height; pl.inc = &inc; pl.p = &p; pl.nb = &nb;
-        pl.max_height = F.max_height; pl.ks = KS; pl.min_sub = min_sub; pl.seg_rows = kSubSegRows;
-        pl.node_bytes = (long long)sizeof(SubNode);
-        cut_height_ = choose_cut_height(pl);
-    }
-    std::vector<char> fused(nn_, 0);
-    {
-        std::vector<SubNode> snodes;
-        std::vector<SubLevel> slevels;
-        std::vector<SubTree> strees;
-        std::vector<int> items;
-        std::vector<long long> items2;
-        std::vector<int> fidx(nn_, -1), bidx(nn_, -1);   // forward / backward record of every fused supernode
-        std::vector<std::vector<int>> sub_all;      // supernodes of every subtree (root first)
-        sub_lds_f_ = sub_lds_b_ = 0;
-        if (cut_height_ >= 0) {
-            for (int rt : roots_at(cut_height_)) {
-                std::vector<int> all = collect(rt);
-                const int H = F.height[rt];
-                SubTree T{(int)slevels.size(), H + 1, (int)snodes.size(), 0};
-                for (int h = 0; h <= H; ++h) {
-                    SubLevel L{};
-                    L.n0 = (int)snodes.size();
-                    int lf = 0, lb = 0;
-                    std::vector<int> lv;
-                    for (int v : all) if (F.height[v] == h) lv.push_back(v);
-                    std::sort(lv.begin(), lv.end());
-                    for (int v : lv) {
-                        fused[v] = 1;
-                        SubNode nd{};
-                        nd.p = p[v]; nd.nb = nb[v]; nd.beg = beg[v]; nd.bnd_off = bnd_off[v]; nd.ell_w = ell_w[v];
-                        nd.lds = 0; nd.goff = goff[v]; nd.uoff = uoff[v]; nd.ell_off = ell_off[v]; nd.ldr = ldr[v];
-                        nd.slot = -1;   // forward copy: LDS update-vector slot (kSubU, set below)
-                        nd.xo = -1;
-                        fidx[v] = (int)snodes.size();
-                        snodes.push_back(nd);
-                    }
-                    // forward: f_P offsets, assembly items, row items
-                    L.fa0 = (int)items.size();
-                    for (size_t k = 0; k < lv.size(); ++k) {
-                        snodes[L.n0 + k].lds = lf / 8;
-                        for (int c = 0; c < p[lv[k]]; ++c) items.push_back(((int)k << 16) | c);
-                        lf += 24 * p[lv[k]];
-                    }
-                    L.nfa = (int)items.size() - L.fa0;
-                    L.fr0 = (int)items.size();
-                    for (size_t k = 0; k < lv.size(); ++k)
-                        for (int r = 0; r < p[lv[k]] + nb[lv[k]]; ++r) items.push_back(((int)k << 16) | r);
-                    L.nfr = (int)items.size() - L.fr0;
-                    // backward: the same supernodes with their [y_P ; -x_B] vectors; the LDS
-                    // offsets differ, so the backward items address a second copy of the nodes
-                    const int n1 = (int)snodes.size();
-                    for (size_t k = 0; k < lv.size(); ++k) {
-                        SubNode nd = snodes[L.n0 + k];
-                        bidx[lv[k]] = (int)snodes.size();
-                        nd.lds = lb / 8;
-                        lb += 24 * (p[lv[k]] + nb[lv[k]]);
-                        snodes.push_back(nd);
-                    }
-                    L.bv0 = (int)items.size();
-                    for (size_t k = 0; k < lv.size(); ++k)
-                        for (int r = 0; r < p[lv[k]] + nb[lv[k]]; ++r) items.push_back(((int)(k + (n1 - L.n0)) << 16) | r);
-                    L.nbv = (int)items.size() - L.bv0;
-                    // segment partial slots after the level's vectors; items (node, segment, column)
-                    L.bs0 = (int)items2.size();
-                    for (size_t k = 0; k < lv.size(); ++k) {
-                        SubNode& nd = snodes[n1 + k];
-                        nd.slot = lb / 8;
-                        const int pp = p[lv[k]], RR = pp + nb[lv[k]];
-                        for (int sg = 0; sg * kSubSegRows < RR; ++sg) {
-                            const int nc = std::min(pp, (sg + 1) * kSubSegRows);
-                            for (int j = 0; j < nc; ++j)
-                                items2.push_back(((long long)(k + (n1 - L.n0)) << 40) | ((long long)sg << 20) | j);
-                            lb += 24 * nc;
-                        }
-                    }
-                    L.nbs = (int)items2.size() - L.bs0;
-                    L.bc0 = (int)items.size();
-                    for (size_t k = 0; k < lv.size(); ++k)
-                        for (int j = 0; j < p[lv[k]]; ++j) items.push_back(((int)(k + (n1 - L.n0)) << 16) | j);
-                    L.nbc = (int)items.size() - L.bc0;
-                    sub_lds_f_ = std::max(sub_lds_f_, lf);
-                    sub_lds_b_ = std::max(sub_lds_b_, lb);
-                    slevels.push_back(L);
-                }
-                T.nnode = (int)snodes.size() - T.node0;
-                sub_nodes_max_ = std::max(sub_nodes_max_, T.nnode);
-                strees.push_back(T);
-                sub_all.push_back(std::move(all));
-            }
-        }
-        n_sub_ = (int)strees.size();
-        plan_sub_lds(F, kids, p, nb, beg, uoff, bnd_off, ell_w, ell_off, ell, bnd, fidx, bidx, sub_all, strees, snodes, KS,
-                     stats, s);
-        plan_ = PlanSummary{};
-        for (const SubTree& T : strees) { plan_.sub_u += (T.flags & kSubU) != 0; plan_.sub_x += (T.flags & kSubX) != 0; }
-        // ---- branches (AA_SOLVE_BRANCHES, see direct_solve.hpp): disjoint subtrees of the tree
-        // solved on parallel streams, the supernodes above them ("top") after the join
-        plan_branches(F, inc, fused, kids, p, nb, stats);
-        if (nbr_ > 1) {
-            int dev = 0;
-            AA_HIP(hipStreamGetDevice(s, &dev));
-            for (int b = 0; b < nbr_; ++b) side_[b].create(dev);
-        }
-        sub_rng_.assign(nbr_ + 1, {0, 0});
-        if (nbr_ > 1) {   // fused subtrees grouped by branch (a SubTree is self-contained: reorder freely)
-            std::vector<int> ord(strees.size());
-            for (size_t t = 0; t < ord.size(); ++t) ord[t] = (int)t;
-            std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return brn_[sub_all[a][0]] < brn_[sub_all[b][0]]; });
-            std::vector<SubTree> st2;
-            for (int t : ord) st2.push_back(strees[t]);
-            strees.swap(st2);
-            for (size_t k = 0; k < ord.size(); ++k) {
-                const int b = brn_[sub_all[ord[k]][0]];
-                if (b < 0 || b >= nbr_) throw Error(ERR_STATE, "DirectSolver: fused subtree outside the branches");
-                if (sub_rng_[b].second == 0) sub_rng_[b].first = (int)k;
-                ++sub_rng_[b].second;
-            }
-        } else {
-            sub_rng_[0] = {0, n_sub_};
-        }
-        if (stats) {
-            double by = 0;
-            int nsn = 0;
-            for (int sn = 0; sn < nn_; ++sn)
-                if (fused[sn]) { by += 8.0 * (0.5 * p[sn] * (p[sn] + 1.0) + (double)p[sn] * nb[sn]); ++nsn; }
-            std::fprintf(stderr, "[solve] fused subtrees: %d (cut height %d), %d supernodes, %.2f MB/sweep, lds f %d b %d\n",
-                         n_sub_, cut_height_, nsn, by / 1e6, sub_lds_f_, sub_lds_b_);
-            // per height inside the subtrees: supernodes, rows, the longest forward row loop (p)
-            // and bytes -- a level's time is bounded below by its longest serial loop
-            for (int h = 0; h <= cut_height_; ++h) {
-                long long cnt = 0, rows = 0, maxp = 0, maxR = 0;
-                double bh = 0;
-                for (int sn = 0; sn < nn_; ++sn) {
-                    if (!fused[sn] || F.height[sn] != h) continue;
-                    ++cnt; rows += p[sn] + nb[sn];
-                    maxp = std::max<long long>(maxp, p[sn]); maxR = std::max<long long>(maxR, p[sn] + nb[sn]);
-                    bh += 8.0 * (0.5 * p[sn] * (p[sn] + 1.0) + (double)p[sn] * nb[sn]);
-                }
-                std::fprintf(stderr, "[solve]   sub height %d: %lld supernodes, %.1f rows/subtree, max p %lld, max R %lld, %.2f MB\n",
-                             h, cnt, n_sub_ ? (double)rows / n_sub_ : 0.0, maxp, maxR, bh / 1e6);
-            }
-        }
-        sub_nodes_.upload(snodes, s);
-        sub_levels_.upload(slevels, s);
-        sub_trees_.upload(strees, s);
-        sub_items_.upload(items, s);
-        sub_items2_.upload(items2, s);
-    }
-    // levels by height and their row tasks
-    // partitioned: the shared top as ONE dense root supernode (nested_dissection merge_top) is
-    // split over the GPUs by rows instead of being solved whole on each
-    top_sn_ = -1;
-    if (comm_) {
-        int ntop = 0, cand = -1;
-        for (int sn = 0; sn < nn_; ++sn)
-            if ((*node_part)[sn] == -1 && p[sn] > 0) { ++ntop; cand = sn; }
-        if (ntop == 1 && F.parent[cand] < 0 && nb[cand] == 0 && beg[cand] == top_beg_ && p[cand] == n_ - top_beg_ &&
-            !fused[cand])
-            top_sn_ = cand;
-    }
-    std::vector<std::vector<int>> hl(F.max_height + 1);
-    for (int sn = 0; sn < nn_; ++sn) if (!fused[sn] && inc[sn] && sn != top_sn_) hl[F.height[sn]].push_back(sn);
-    std::vector<Task> tasks;
-    std::vector<BTile> btiles;
-    std::vector<BRed> breds;
-    std::vector<FTile> ftiles;
-    std::vector<FRed> freds;
-    std::vector<int> fwid, bwid;   // tile widths (packing)
-    std::vector<int> ft_sn, fr_sn, bt_sn, br_sn;   // supernode of every tile / reduction (streams)
-    std::vector<int> lev_of(nn_, -1);              // level of every level-scheduled supernode
-    long long poff = 0;
-    auto mk = [&](int sn, int r0, int nr) {
-        Task t{};
-        t.node = sn; t.r0 = r0; t.nr = nr;
-        t.p = p[sn]; t.nb = nb[sn]; t.beg = beg[sn]; t.bnd_off = bnd_off[sn];
-        t.ell_w = ell_w[sn];
-        t.goff = goff[sn]; t.uoff = uoff[sn]; t.ell_off = ell_off[sn]; t.ldr = ldr[sn];
-        return t;
-    };
-    levels_.clear();
-    kernels_ = 0;
+    return Gr;
+}
 
-    int max_lds = 0;
-    lbr_.clear();
-    for (auto& l : hl) {
-        if (l.empty()) continue;
-        if (nbr_ > 1)   // contiguous per branch (then the top): every launch below takes a range
-            std::stable_sort(l.begin(), l.end(), [&](int a, int b) { return brn_[a] < brn_[b]; });
-        Level L;
-        int fr = 0, br = 0;
-        bool fwave = false, bwave = false;
-        for (int sn : l) {
-            const int R = p[sn] + nb[sn];
-            if (p[sn] <= wave_p_) fr = std::max(fr, R);
-            if (R <= wave_r_) br = std::max(br, p[sn]);
-        }
-        (void)fwave;
-        L.fblock = fr > 128 ? 256 : (fr > 64 ? 128 : 64);
-        (void)bwave;
-        L.bblock = br > 128 ? 256 : (br > 64 ? 128 : 64);
-        L.fwd_first = (int)tasks.size();
-        for (int sn : l) {
-            const int R = p[sn] + nb[sn];
-            if (p[sn] <= wave_p_) {
-                for (int r0 = 0; r0 < R; r0 += L.fblock) tasks.push_back(mk(sn, r0, std::min(L.fblock, R - r0)));
-                L.lds_fwd = std::max(L.lds_fwd, 24 * p[sn]);
-            }
-        }
-        L.fwd_count = (int)tasks.size() - L.fwd_first;
-        // tile widths of this level (see min_tiles above)
-        auto pick = [&](auto count) {
-            if (tw) return std::atoi(tw) >= 256 ? 256 : (std::atoi(tw) >= 128 ? 128 : 64);
-            if (min_tiles <= 0) return 256;
-            for (int w : {256, 128}) if (count(w) >= min_tiles) return w;
-            return 64;
-        };
-        L.ftw = pick([&](int w) {
-            long long n = 0;
-            for (int sn : l) {
-                if (p[sn] <= wave_p_) continue;
-                const int R = p[sn] + nb[sn];
-                for (int r0 = 0; r0 < R; r0 += 64) n += std::min((r0 + 63) / w + 1, (p[sn] + w - 1) / w);
-            }
-            return n;
-        });
-        L.btw = pick([&](int w) {
-            long long n = 0;
-            for (int sn : l) {
-                const int R = p[sn] + nb[sn];
-                if (R <= wave_r_) continue;
-                for (int c0 = 0; c0 < p[sn]; c0 += 128) n += (R - c0 + w - 1) / w;
-            }
-            return n;
-        });
-        const int ftw = L.ftw, btw = L.btw;
-        // large supernodes: split-K forward tiles (64 rows x ftw columns; tiles entirely
-        // above the diagonal of L_PP^-1 are zero and skipped), one reduction task per row block
-        L.ft_first = (int)ftiles.size();
-        L.fr_first = (int)freds.size();
-        for (int sn : l) {
-            if (p[sn] <= wave_p_) continue;
-            const int R = p[sn] + nb[sn];
-            for (int r0 = 0; r0 < R; r0 += 64) {
-                FRed rd{};
-                rd.beg = beg[sn]; rd.p = p[sn]; rd.r0 = r0; rd.nr = std::min(64, R - r0);
-                rd.uoff = uoff[sn]; rd.ell_off = ell_off[sn]; rd.ell_w = ell_w[sn]; rd.poff = poff;
-                for (int c0 = 0; c0 < p[sn]; c0 += ftw) {
-                    if (r0 + 63 < c0) break;
-                    FTile ft{};
-                    ft.beg = beg[sn]; ft.p = p[sn]; ft.R = R; ft.c0 = c0; ft.r0 = r0;
-                    ft.nc = std::min(ftw, p[sn] - c0);
-                    ft.goff = goff[sn]; ft.ell_off = ell_off[sn]; ft.ell_w = ell_w[sn]; ft.poff = poff;
-                    ft.rid = (int)freds.size();
-                    poff += 3 * 64;
-                    ftiles.push_back(ft);
-                    fwid.push_back(ftw);
-                    ft_sn.push_back(sn);
-                    ++rd.nt;
-                }
-                freds.push_back(rd);
-                fr_sn.push_back(sn);
-            }
-        }
-        L.ft_count = (int)ftiles.size() - L.ft_first;
-        L.frd_count = (int)freds.size() - L.fr_first;
-        L.bwd_first = (int)tasks.size();
-        for (int sn : l) {
-            const int R = p[sn] + nb[sn];
-            if (R <= wave_r_) {
-                for (int j0 = 0; j0 < p[sn]; j0 += L.bblock) tasks.push_back(mk(sn, j0, std::min(L.bblock, p[sn] - j0)));
-                L.lds_bwd = std::max(L.lds_bwd, 24 * R);
-            }
-        }
-        L.bwd_count = (int)tasks.size() - L.bwd_first;
-        // large supernodes: split-K tiles (128 columns x btw rows; the tiles above the
-        // diagonal of L_PP^-1 are all zero and skipped) and one reduction task per column block
-        L.bt_first = (int)btiles.size();
-        L.br_first = (int)breds.size();
-        for (int sn : l) {
-            const int R = p[sn] + nb[sn];
-            if (R <= wave_r_) continue;
-            for (int c0 = 0; c0 < p[sn]; c0 += 128) {
-                BRed rd{};
-                rd.beg = beg[sn]; rd.c0 = c0; rd.nc = std::min(128, p[sn] - c0); rd.poff = poff;
-                for (int r0 = c0; r0 < R; r0 += btw) {
-                    BTile bt{};
-                    bt.beg = beg[sn]; bt.p = p[sn]; bt.nb = nb[sn]; bt.bnd_off = bnd_off[sn];
-                    bt.c0 = c0; bt.r0 = r0; bt.nr = std::min(btw, R - r0);
-                    bt.goff = goff[sn]; bt.poff = poff; bt.ldr = ldr[sn];
-                    bt.rid = (int)breds.size();
-                    poff += 6 * 64;
-                    btiles.push_back(bt);
-                    bwid.push_back(btw);
-                    bt_sn.push_back(sn);
-                    ++rd.nt;
-                }
-                breds.push_back(rd);
-                br_sn.push_back(sn);
-            }
-        }
-        L.bt_count = (int)btiles.size() - L.bt_first;
-        L.br_count = (int)breds.size() - L.br_first;
-        max_lds = std::max(max_lds, std::max(L.lds_fwd, L.lds_bwd));
-        kernels_ += (L.fwd_count ? 1 : 0) + (L.bwd_count ? 1 : 0) + (L.bt_count ? 1 : 0) + (L.ft_count ? 1 : 0);
-        {   // per branch (and the top, slot nbr_): the sub-ranges of this level's four launches
-            auto ranges = [&](int first, int count, auto node_of, int BrRange::*f, int BrRange::*c, size_t base) {
-                for (int k = first; k < first + count; ++k) {
-                    const int b = nbr_ > 1 ? brn_[node_of(k)] : 0;
-                    BrRange& r = lbr_[base + b];
-                    if (r.*c == 0) r.*f = k;
-                    else if (r.*f + r.*c != k) throw Error(ERR_STATE, "DirectSolver: branch ranges not contiguous");
-                    ++(r.*c);
-                }
-            };
-            const size_t base = lbr_.size();
-            lbr_.resize(base + nbr_ + 1);
-            ranges(L.fwd_first, L.fwd_count, [&](int k) { return tasks[k].node; }, &BrRange::fwd_first, &BrRange::fwd_count, base);
-            ranges(L.ft_first, L.ft_count, [&](int k) { return ft_sn[k]; }, &BrRange::ft_first, &BrRange::ft_count, base);
-            ranges(L.bwd_first, L.bwd_count, [&](int k) { return tasks[k].node; }, &BrRange::bwd_first, &BrRange::bwd_count, base);
-            ranges(L.bt_first, L.bt_count, [&](int k) { return bt_sn[k]; }, &BrRange::bt_first, &BrRange::bt_count, base);
-        }
-        levels_.push_back(L);
-        for (int sn : l) lev_of[sn] = (int)levels_.size() - 1;
-        if (stats) {
-            double by = 0;
-            int maxp = 0, maxnb = 0, nw = 0;
-            for (int sn : l) {
-                by += 8.0 * (0.5 * p[sn] * (p[sn] + 1.0) + (double)p[sn] * nb[sn]);
-                maxp = std::max(maxp, p[sn]); maxnb = std::max(maxnb, nb[sn]);
-                nw += p[sn] > wave_p_;
-            }
-            std::fprintf(stderr, "[solve] level %zu: %zu supernodes (%d tiled), max p %d, max nb %d, %.2f MB/sweep, "
-                         "fwd tasks %d (blk %d) fwd tiles %d (w %d) bwd tasks %d (blk %d) bwd tiles %d (w %d)\n",
-                         levels_.size() - 1, l.size(), nw, maxp, maxnb, by / 1e6, L.fwd_count, L.fblock, L.ft_count, L.ftw,
-                         L.bwd_count, L.bblock, L.bt_count, L.btw);
-        }
+template <class T>
+void drop(std::vector<T>& v) { std::vector<T>().swap(v); }
+
+}  // namespace
+
+// The factor on the device: the row-major copy Gr from the host, the column-major copy Gc
+// transposed from it (32 x 32 tiles), and the packed tiles Gt gathered from it in consumption
+// order (see k_fwd_ptile)
+void DirectSolver::upload_factor(const SupernodalFactor& F, hipStream_t s) {
+    const SolvePlan& P = pl_;
+    const std::unique_ptr<double[]> Gr = form_gr(F, P);
+    Gr_.upload(Gr.get(), (size_t)P.g_doubles, s);
+    Gc_.alloc((size_t)P.g_doubles);
+    std::vector<TrTile> tt;
+    for (int sn = 0; sn < P.nn; ++sn) {
+        if (!P.inc[sn]) continue;
+        const int R = P.p[sn] + P.nb[sn];
+        for (int r0 = 0; r0 < R; r0 += 32)
+            for (int c0 = 0; c0 < P.p[sn]; c0 += 32) tt.push_back(TrTile{P.goff[sn], R, P.ldr[sn], P.p[sn], r0, c0});
     }
-    if (top_sn_ >= 0) {
-        // rows [top_r0_, top_r1_) of the top triangle, in kTopBlk blocks, equal areas per GPU
-        const int sn = top_sn_, P = comm_->size(), me = comm_->rank(), pt = p[sn];
-        const int nblk = (pt + kTopBlk - 1) / kTopBlk;
-        const double total = 0.5 * pt * (pt + 1.0);
-        std::vector<int> cut(P + 1, nblk);
-        cut[0] = 0;
-        double acc = 0;
-        int r = 1;
-        for (int b = 0; b < nblk && r < P; ++b) {
-            const double r0 = (double)b * kTopBlk, r1 = std::min<double>(pt, r0 + kTopBlk);
-            acc += 0.5 * (r1 * (r1 + 1) - r0 * (r0 + 1));
-            while (r < P && acc >= total * r / P) cut[r++] = b + 1;
-        }
-        top_p_ = pt;
-        top_r0_ = std::min(pt, cut[me] * kTopBlk);
-        top_r1_ = std::min(pt, cut[me + 1] * kTopBlk);
-        top_task_ = mk(sn, 0, pt);
-        top_ftw_ = tw ? (std::atoi(tw) >= 256 ? 256 : (std::atoi(tw) >= 128 ? 128 : 64)) : 256;
-        top_btw_ = top_ftw_;
-        // forward tiles of the own rows (64-row blocks); the front is read summed from top_f_
-        top_ft_first_ = (int)ftiles.size();
-        for (int r0 = top_r0_; r0 < top_r1_; r0 += 64) {
-            FRed rd{};
-            rd.beg = beg[sn]; rd.p = pt; rd.r0 = r0; rd.nr = std::min(64, top_r1_ - r0);
-            rd.uoff = uoff[sn]; rd.ell_off = 0; rd.ell_w = 0; rd.poff = poff;
-            for (int c0 = 0; c0 < pt; c0 += top_ftw_) {
-                if (r0 + 63 < c0) break;
-                FTile ft{};
-                ft.beg = beg[sn]; ft.p = pt; ft.R = pt; ft.c0 = c0; ft.r0 = r0;
-                ft.nc = std::min(top_ftw_, pt - c0);
-                ft.goff = goff[sn]; ft.ell_off = 0; ft.ell_w = 0; ft.poff = poff;
-                ft.rid = (int)freds.size();
-                poff += 3 * 64;
-                ftiles.push_back(ft);
-                fwid.push_back(top_ftw_);
-                ft_sn.push_back(sn);
-                ++rd.nt;
-            }
-            freds.push_back(rd);
-            fr_sn.push_back(sn);
-        }
-        top_ft_count_ = (int)ftiles.size() - top_ft_first_;
-        // backward: the products of the own rows only (partial x_top, summed over the GPUs)
-        top_bt_first_ = (int)btiles.size();
-        for (int c0 = 0; c0 < top_r1_; c0 += 128) {
-            const int rs = std::max(c0, top_r0_);
-            if (rs >= top_r1_) continue;
-            BRed rd{};
-            rd.beg = beg[sn]; rd.c0 = c0; rd.nc = std::min(128, pt - c0); rd.poff = poff;
-            for (int r0 = rs; r0 < top_r1_; r0 += top_btw_) {
-                BTile bt{};
-                bt.beg = beg[sn]; bt.p = pt; bt.nb = 0; bt.bnd_off = bnd_off[sn];
-                bt.c0 = c0; bt.r0 = r0; bt.nr = std::min(top_btw_, top_r1_ - r0);
-                bt.goff = goff[sn]; bt.poff = poff; bt.ldr = ldr[sn];
-                bt.rid = (int)breds.size();
-                poff += 6 * 64;
-                btiles.push_back(bt);
-                bwid.push_back(top_btw_);
-                bt_sn.push_back(sn);
-                ++rd.nt;
-            }
-            breds.push_back(rd);
-            br_sn.push_back(sn);
-        }
-        top_bt_count_ = (int)btiles.size() - top_bt_first_;
-        kernels_ += 4;
-        // bytes: this GPU streams its row slice of the triangle (twice), not the whole top
-        const double whole = 0.5 * pt * (pt + 1.0), a0 = top_r0_, a1 = top_r1_;
-        dense -= whole;
-        dense += 0.5 * (a1 * (a1 + 1) - a0 * (a0 + 1));
-        top_task_d_.upload(std::vector<Task>{top_task_}, s);
-        top_f_.alloc(3 * (size_t)KS * pt);
-        top_x_.alloc(3 * (size_t)KS * pt);
-        if (stats)
-            std::fprintf(stderr, "[solve] dense top: %d rows, this GPU rows [%d, %d), fwd tiles %d, bwd tiles %d\n", pt,
-                         top_r0_, top_r1_, top_ft_count_, top_bt_count_);
-    }
-    if (n_sub_) kernels_ += 2;
-    if (const char* st = std::getenv("AA_SUB_TIMING")) {
-        sub_timing_ = std::atoi(st);
-        if (sub_timing_ > 0 && n_sub_ > 0) { sub_clk_.alloc(2 * 64 * (size_t)n_sub_); sub_clk_.zero(s); }
-        if (cut_height_ + 1 > 21) sub_timing_ = 0;   // 64 clock slots per workgroup
-    }
-    bnd_.upload(bnd, s);
-    ell_.upload(ell, s);
-    Gr_.upload(Gr.get(), (size_t)go, s);
-    Gc_.alloc((size_t)go);
-    {   // Gc (column-major R x p per supernode) = transpose of Gr (row-major R x ldr), 32 x 32 tiles
-        std::vector<TrTile> tt;
-        for (int sn = 0; sn < nn_; ++sn) {
-            if (!inc[sn]) continue;
-            const int R = p[sn] + nb[sn];
-            for (int r0 = 0; r0 < R; r0 += 32)
-                for (int c0 = 0; c0 < p[sn]; c0 += 32) tt.push_back(TrTile{goff[sn], R, ldr[sn], p[sn], r0, c0});
-        }
-        if (!tt.empty()) {
-            DevBuf<TrTile> dt;
-            dt.upload(tt, s);
-            hipLaunchKernelGGL(k_gr_to_gc, dim3((unsigned)tt.size()), dim3(32, 8), 0, s, dt.p, Gr_.p, Gc_.p);
-            AA_CHECK_LAUNCH();
-            AA_HIP(hipStreamSynchronize(s));
-        }
-    }
-    // packed tiles: every tile's block in consumption order (see k_fwd_ptile), built on the
-    // device from Gr; AA_SOLVE_PACKED=0 keeps the tiles on the strided copies (A/B)
-    {
-        const char* pk = std::getenv("AA_SOLVE_PACKED");
-        packed_ = !(pk && pk[0] == '0');
-    }
-    if (packed_ && (!ftiles.empty() || !btiles.empty())) {
-        long long to = 0;
-        for (size_t i = 0; i < ftiles.size(); ++i) { ftiles[i].toff = to; to += 64LL * fwid[i]; }
-        for (size_t i = 0; i < btiles.size(); ++i) {   // narrow blocks (<= 64 columns): half (k_pack_btiles)
-            btiles[i].toff = to;
-            to += (btiles[i].p - btiles[i].c0 <= 64 ? 64LL : 128LL) * bwid[i];
-        }
-        Gt_.alloc((size_t)to);
-        DevBuf<FTile> dft;
-        DevBuf<BTile> dbt;
-        DevBuf<int> dfw, dbw;
-        if (!ftiles.empty()) {
-            dft.upload(ftiles, s);
-            dfw.upload(fwid, s);
-            hipLaunchKernelGGL(k_pack_ftiles, dim3((unsigned)ftiles.size()), dim3(256), 0, s, dft.p, dfw.p, Gr_.p, Gt_.p);
-            AA_CHECK_LAUNCH();
-        }
-        if (!btiles.empty()) {
-            dbt.upload(btiles, s);
-            dbw.upload(bwid, s);
-            hipLaunchKernelGGL(k_pack_btiles, dim3((unsigned)btiles.size()), dim3(256), 0, s, dbt.p, dbw.p, Gr_.p, Gt_.p);
-            AA_CHECK_LAUNCH();
-        }
+    if (!tt.empty()) {
+        DevBuf<TrTile> dt;
+        dt.upload(tt, s);
+        hipLaunchKernelGGL(k_gr_to_gc, dim3((unsigned)tt.size()), dim3(32, 8), 0, s, dt.p, Gr_.p, Gc_.p);
+        AA_CHECK_LAUNCH();
         AA_HIP(hipStreamSynchronize(s));
-        if (stats) std::fprintf(stderr, "[solve] packed tiles: %zu forward, %zu backward, %.1f MB\n", ftiles.size(),
-                                btiles.size(), 8e-6 * (double)to);
-    } else {
-        packed_ = false;
     }
-    // ---- streamed tile levels (see Stream in direct_solve.hpp): maximal runs of >= 2 consecutive
-    // levels with packed split-K tiles only and one tile width. Forward: a tile of supernode s waits
-    // for every update-row reduction of its children in the same run; backward: for every
-    // reduction of its parent in the same run (the parent's rows and, through the parent's own
-    // wait, all its ancestors' rows in the run).
-    {
-        const char* st = std::getenv("AA_SOLVE_STREAM");
-        stream_ = packed_ && st && st[0] == '1';   // measured slower on C4: opt-in
-        // a gated solve that is skipped (the Anderson reject path's, most iterations) costs one
-        // dependent launch (~4.6 us in a graph) per level: its tile runs as one launch each cut
-        // that; taken, a streamed run is slower than its levels
-        const char* sg = std::getenv("AA_SOLVE_STREAM_GATED");
-        stream_gated_ = packed_ && !node_part && (sg ? sg[0] == '1' : true);   // (one GPU)
+    if (!P.packed) return;
+    Gt_.alloc((size_t)P.gt_doubles);
+    DevBuf<FTile> dft;
+    DevBuf<BTile> dbt;
+    DevBuf<int> dfw, dbw;
+    if (!P.ftiles.empty()) {
+        dft.upload(P.ftiles, s);
+        dfw.upload(P.fwid, s);
+        hipLaunchKernelGGL(k_pack_ftiles, dim3((unsigned)P.ftiles.size()), dim3(256), 0, s, dft.p, dfw.p, Gr_.p, Gt_.p);
+        AA_CHECK_LAUNCH();
     }
-    stream_plan_ = stream_ || stream_gated_;
-    fstreams_.clear();
-    bstreams_.clear();
-    std::vector<int> forder, border, bndx(bnd.size(), -1);
-    long long xs_rows = 0;
-    if (stream_plan_) {
-        const int nL = (int)levels_.size();
-        auto runs = [&](bool fwd) {
-            std::vector<std::pair<int, int>> r;
-            for (int i = 0; i < nL;) {
-                auto ok = [&](int l) {
-                    const Level& L = levels_[l];
-                    return fwd ? (L.fwd_count == 0 && L.ft_count > 0) : (L.bwd_count == 0 && L.bt_count > 0);
-                };
-                auto wid = [&](int l) { return fwd ? levels_[l].ftw : levels_[l].btw; };
-                if (!ok(i)) { ++i; continue; }
-                int j = i + 1;
-                while (j < nL && ok(j) && wid(j) == wid(i)) ++j;
-                if (j - i >= 2) r.push_back({i, j});
-                i = j;
-            }
-            return r;
-        };
-        const auto fr = runs(true), br = runs(false);
-        n_heads_ = (int)(fr.size() + br.size());
-        const int CF = n_heads_, CB = n_heads_ + nn_;   // counter bases in sync_
-        std::vector<int> nfr_b(nn_, 0), nbr(nn_, 0);     // per supernode: update-row / all reductions
-        for (size_t i = 0; i < freds.size(); ++i)
-            if (freds[i].r0 + freds[i].nr > freds[i].p) ++nfr_b[fr_sn[i]];
-        for (size_t i = 0; i < breds.size(); ++i) ++nbr[br_sn[i]];
-        int head = 0;
-        for (const auto& run : fr) {
-            const int l0 = run.first, l1 = run.second;
-            auto in = [&](int sn) { return sn >= 0 && lev_of[sn] >= l0 && lev_of[sn] < l1; };
-            Stream S{l0, l1, (int)forder.size(), 0, head++};
-            for (int l = l0; l < l1; ++l)
-                for (int k = 0; k < levels_[l].ft_count; ++k) forder.push_back(levels_[l].ft_first + k);
-            S.count = (int)forder.size() - S.first;
-            for (int k = S.first; k < S.first + S.count; ++k) {
-                FTile& ft = ftiles[forder[k]];
-                const int sn = ft_sn[forder[k]];
-                int need = 0;
-                for (int c : kids[sn]) if (in(c)) need += nfr_b[c];
-                ft.dep = CF + sn;
-                ft.need = need;
-            }
-            for (size_t i = 0; i < freds.size(); ++i) {
-                const int sn = fr_sn[i];
-                if (!in(sn)) continue;
-                const int par = F.parent[sn];
-                freds[i].sig = (in(par) && freds[i].r0 + freds[i].nr > freds[i].p) ? CF + par : -1;
-            }
-            fstreams_.push_back(S);
-        }
-        std::vector<int> node_sn(n_, -1), xso(nn_, -1);
-        for (int sn = 0; sn < nn_; ++sn)
-            for (int i = F.beg[sn]; i < F.end[sn] && i < n_; ++i) node_sn[i] = sn;
-        for (auto it = br.rbegin(); it != br.rend(); ++it) {   // processing order: top runs first
-            const int l0 = it->first, l1 = it->second;
-            auto in = [&](int sn) { return sn >= 0 && lev_of[sn] >= l0 && lev_of[sn] < l1; };
-            Stream S{l0, l1, (int)border.size(), 0, head++};
-            for (int l = l1 - 1; l >= l0; --l)
-                for (int k = 0; k < levels_[l].bt_count; ++k) border.push_back(levels_[l].bt_first + k);
-            S.count = (int)border.size() - S.first;
-            std::vector<char> has_kid(nn_, 0);
-            for (int l = l0; l < l1; ++l)
-                for (int k = 0; k < levels_[l].bt_count; ++k) {
-                    const int sn = bt_sn[levels_[l].bt_first + k];
-                    if (in(F.parent[sn])) has_kid[F.parent[sn]] = 1;
-                }
-            for (int k = S.first; k < S.first + S.count; ++k) {
-                BTile& bt = btiles[border[k]];
-                const int sn = bt_sn[border[k]], par = F.parent[sn];
-                bt.dep = in(par) ? CB + par : -1;
-                bt.need = in(par) ? nbr[par] : 0;
-                if (has_kid[sn] && xso[sn] < 0) { xso[sn] = (int)xs_rows; xs_rows += (p[sn] + 15) / 16 * 16; }
-            }
-            for (size_t i = 0; i < breds.size(); ++i) {
-                const int sn = br_sn[i];
-                if (!in(sn)) continue;
-                breds[i].sig = has_kid[sn] ? CB + sn : -1;
-                breds[i].xso = xso[sn];
-            }
-            // boundary rows of this run's supernodes owned by supernodes of the run: read from Xs
-            for (int l = l0; l < l1; ++l)
-                for (int k = 0; k < levels_[l].bt_count; ++k) {
-                    const int sn = bt_sn[levels_[l].bt_first + k];
-                    for (int a = 0; a < nb[sn]; ++a) {
-                        const int node = F.bnd[sn][a], ow = node < n_ ? node_sn[node] : -1;
-                        if (ow >= 0 && in(ow) && xso[ow] >= 0) bndx[bnd_off[sn] + a] = xso[ow] + (node - beg[ow]);
-                    }
-                }
-            bstreams_.push_back(S);
-        }
-        if (stats)
-            for (auto& S : fstreams_)
-                std::fprintf(stderr, "[solve] streamed forward levels [%d, %d): %d tiles, one launch\n", S.l0, S.l1, S.count);
-        if (stats)
-            for (auto& S : bstreams_)
-                std::fprintf(stderr, "[solve] streamed backward levels [%d, %d): %d tiles, one launch\n", S.l0, S.l1, S.count);
-        if (fstreams_.empty() && bstreams_.empty()) stream_ = stream_gated_ = stream_plan_ = false;
-    }
-    if (stream_plan_) {
-        forder_.upload(forder.empty() ? std::vector<int>{0} : forder, s);
-        border_.upload(border.empty() ? std::vector<int>{0} : border, s);
-        bndx_.upload(bndx.empty() ? std::vector<int>{-1} : bndx, s);
-        sync_.alloc((size_t)n_heads_ + 2 * (size_t)nn_);
-        sync_.zero(s);
-        Xs_.alloc(std::max<long long>(3 * KS * xs_rows, 3));
-    }
-    tasks_.upload(tasks, s);
-    btiles_.upload(btiles, s);
-    ftiles_.upload(ftiles, s);
-    freds_.upload(freds, s);
-    fcnt_.alloc(std::max<size_t>(freds.size(), 1)); fcnt_.zero(s);
-    bcnt_.alloc(std::max<size_t>(breds.size(), 1)); bcnt_.zero(s);
-    breds_.upload(breds, s);
-    bpart_.alloc(std::max<long long>(KS * poff, 3));
-    Y_.alloc(3 * KS * (size_t)n_);
-    U_.alloc(std::max<long long>(KS * uo, 3));
-    // (LDS figures above are per 3 columns; a 6-column solve needs twice as much; + the staged nodes)
-    // internal assert: choose_cut_height budgets exactly this aggregate
-    if (std::max(sub_lds_bytes(KS, true), sub_lds_bytes(KS, false)) > 160 * 1024)
-        throw Error(ERR_STATE, "DirectSolver: internal error: fused subtrees exceed 160 KiB of LDS");
-    if (std::max(sub_lds_bytes(KS, true), sub_lds_bytes(KS, false)) > 64 * 1024)
-        for (const void* k : {(const void*)k_fwd_sub<256, 3, false>, (const void*)k_fwd_sub<512, 3, false>, (const void*)k_fwd_sub<1024, 3, false>,
-                              (const void*)k_bwd_sub<256, 3, false>, (const void*)k_bwd_sub<512, 3, false>, (const void*)k_bwd_sub<1024, 3, false>,
-                              (const void*)k_fwd_sub<256, 6, false>, (const void*)k_fwd_sub<512, 6, false>, (const void*)k_fwd_sub<1024, 6, false>,
-                              (const void*)k_bwd_sub<256, 6, false>, (const void*)k_bwd_sub<512, 6, false>, (const void*)k_bwd_sub<1024, 6, false>,
-                              (const void*)k_fwd_sub<256, 3, true>, (const void*)k_fwd_sub<512, 3, true>, (const void*)k_fwd_sub<1024, 3, true>,
-                              (const void*)k_bwd_sub<256, 3, true>, (const void*)k_bwd_sub<512, 3, true>, (const void*)k_bwd_sub<1024, 3, true>,
-                              (const void*)k_fwd_sub<256, 6, true>, (const void*)k_fwd_sub<512, 6, true>, (const void*)k_fwd_sub<1024, 6, true>,
-                              (const void*)k_bwd_sub<256, 6, true>, (const void*)k_bwd_sub<512, 6, true>, (const void*)k_bwd_sub<1024, 6, true>})
-            AA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (KS * max_lds > 64 * 1024) {   // large fronts: opt in to more than the default 64 KiB of LDS
-        for (const void* k : {(const void*)k_fwd<64, 3, false>, (const void*)k_fwd<128, 3, false>, (const void*)k_fwd<256, 3, false>,
-                              (const void*)k_bwd<64, 3, false>, (const void*)k_bwd<128, 3, false>, (const void*)k_bwd<256, 3, false>,
-                              (const void*)k_fwd<64, 6, false>, (const void*)k_fwd<128, 6, false>, (const void*)k_fwd<256, 6, false>,
-                              (const void*)k_bwd<64, 6, false>, (const void*)k_bwd<128, 6, false>, (const void*)k_bwd<256, 6, false>,
-                              (const void*)k_fwd<64, 3, true>, (const void*)k_fwd<128, 3, true>, (const void*)k_fwd<256, 3, true>,
-                              (const void*)k_bwd<64, 3, true>, (const void*)k_bwd<128, 3, true>, (const void*)k_bwd<256, 3, true>,
-                              (const void*)k_fwd<64, 6, true>, (const void*)k_fwd<128, 6, true>, (const void*)k_fwd<256, 6, true>,
-                              (const void*)k_bwd<64, 6, true>, (const void*)k_bwd<128, 6, true>, (const void*)k_bwd<256, 6, true>})
-            AA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    // algorithmic bytes of one solve: the factor once per sweep (dense triangles + boundary
-    // blocks, fp64), b/y/x (24 B per node each way) and the update vectors (write + read)
-    bytes_ = 2.0 * 8.0 * (dense + offd) + 4.0 * 24.0 * piv + 3.0 * 24.0 * bsum;
-    {   // non-temporal factor loads when a solve's factor stream cannot stay in the Infinity Cache
-        const char* e = std::getenv("AA_FACTOR_NT");
-        nt_ = e ? e[0] == '1' : 2.0 * 8.0 * (dense + offd) > kNtBytes;
-        // the thread-per-row kernels (fused subtrees, row tasks) separately (AA_FACTOR_NT_ROWS):
-        // their 8-B-per-lane loads cover partial lines that a neighbouring wave re-reads, which nt
-        // drops from L2 (PMC, C4: fused backward 1.41 -> 1.81x its factor bytes read). Measured
-        // (same-box A/B): nt on the rows costs C4 (2 GB both sweeps) 33 us and C5 (0.69 GB) 44 us
-        // per solve, and saves C3 (0.28 GB) 12 us -- on only where the factor is within ~2x the
-        // Infinity Cache
-        const char* er = std::getenv("AA_FACTOR_NT_ROWS");
-        nt_rows_ = er ? er[0] == '1' : (nt_ && 2.0 * 8.0 * (dense + offd) < kNtRowsMaxBytes);
-    }
-    bytes2_ = 2.0 * 8.0 * (dense + offd) + 2.0 * (4.0 * 24.0 * piv + 3.0 * 24.0 * bsum);
-    {   // the plan in numbers (plan_summary())
-        PlanSummary& S = plan_;
-        S.supernodes = nn_; S.levels = (int)levels_.size();
-        S.fused_subtrees = n_sub_;
-        for (int sn = 0; sn < nn_; ++sn) S.fused_supernodes += fused[sn] != 0;
-        for (const Level& L : levels_) {
-            S.fwd_tasks += L.fwd_count; S.bwd_tasks += L.bwd_count;
-            S.fwd_tiles += L.ft_count; S.bwd_tiles += L.bt_count;
-            if (L.ft_count) S.fwd_tile_w |= L.ftw;
-            if (L.bt_count) S.bwd_tile_w |= L.btw;
-        }
-        S.fwd_streams = (int)fstreams_.size(); S.bwd_streams = (int)bstreams_.size();
-        S.stream_all = stream_; S.stream_gated = stream_gated_;
-        S.branches = nbr_;
-        S.packed = packed_; S.nt = nt_; S.nt_rows = nt_rows_;
-        auto span = [](int& lo, int& hi, int v, bool first) { lo = first ? v : std::min(lo, v); hi = first ? v : std::max(hi, v); };
-        int nrow = 0, ntile = 0;
-        for (int sn = 0; sn < nn_; ++sn) {
-            if (lev_of[sn] < 0) continue;
-            const int R = p[sn] + nb[sn];
-            const bool frow = p[sn] <= wave_p_, brow = R <= wave_r_;
-            S.fwd_row_nodes += frow; S.fwd_tile_nodes += !frow; S.bwd_row_nodes += brow; S.bwd_tile_nodes += !brow;
-            S.fwd_row_bwd_tile_nodes += frow && !brow; S.fwd_tile_bwd_row_nodes += !frow && brow;
-            S.odd_p_nodes += p[sn] & 1;
-            if (frow && R > levels_[lev_of[sn]].fblock) ++S.multi_block_fwd_nodes;
-            if (frow || brow) { span(S.row_p_min, S.row_p_max, p[sn], nrow == 0); span(S.row_R_min, S.row_R_max, R, nrow == 0); ++nrow; }
-            if (!frow || !brow) { span(S.tile_p_min, S.tile_p_max, p[sn], ntile == 0); span(S.tile_R_min, S.tile_R_max, R, ntile == 0); ++ntile; }
-        }
-        S.sub_block = sub_block_; S.wave_p = wave_p_; S.wave_r = wave_r_; S.max_sets = max_sets_;
+    if (!P.btiles.empty()) {
+        dbt.upload(P.btiles, s);
+        dbw.upload(P.bwid, s);
+        hipLaunchKernelGGL(k_pack_btiles, dim3((unsigned)P.btiles.size()), dim3(256), 0, s, dbt.p, dbw.p, Gr_.p, Gt_.p);
+        AA_CHECK_LAUNCH();
     }
     AA_HIP(hipStreamSynchronize(s));
 }
 
-// dynamic LDS of a fused-subtree launch: the level vectors (K sets), the LDS-resident update
-// vectors (forward) or x rows (backward), then the staged node records
-size_t DirectSolver::sub_lds_bytes(int K, bool fwd) const {
-    const size_t v = (size_t)K * (fwd ? sub_lds_f_ + sub_lds_u_ : sub_lds_b_ + sub_lds_x_);
-    return (v + 15) / 16 * 16 + (size_t)sub_nodes_max_ * sizeof(SubNode);
-}
-
-void DirectSolver::plan_sub_lds(const SupernodalFactor& F, const std::vector<std::vector<int>>& kids,
-                                const std::vector<int>& p, const std::vector<int>& nb, const std::vector<int>& beg,
-                                const std::vector<long long>& uoff, const std::vector<int>& bnd_off,
-                                const std::vector<int>& ell_w, const std::vector<long long>& ell_off,
-                                std::vector<long long>& ell, std::vector<int>& bnd, const std::vector<int>& fidx,
-                                const std::vector<int>& bidx, const std::vector<std::vector<int>>& sub_all, std::vector<SubTree>& strees,
-                                std::vector<SubNode>& snodes, int KS, bool stats, hipStream_t s) {
-    sub_lds_u_ = sub_lds_x_ = 0;
-    const char* eu = std::getenv("AA_SUB_LDS_U");
-    const char* ex = std::getenv("AA_SUB_LDS_X");
-    const bool want_u = !eu || eu[0] != '0', want_x = !ex || ex[0] != '0';
-    // vector bytes (KS sets) a launch may hold: 160 KiB less the staged records
-    const long long cap = (160LL * 1024 - (long long)sub_nodes_max_ * (long long)sizeof(SubNode)) / 16 * 16;
-    const int ubase = sub_lds_f_ / 8, xbase = sub_lds_b_ / 8;   // the regions follow the level vectors
-    std::vector<int> slot(nn_, -1), xg;
-    int nu = 0, nx = 0;
-    for (size_t t = 0; t < sub_all.size(); ++t) {
-        const std::vector<int>& all = sub_all[t];
-        SubTree& T = strees[t];
-        const int rt = all[0];
-        if (want_u) {
-            const int peak = plan_update_slots(all, kids, F.height, nb, slot);
-            if ((long long)KS * (sub_lds_f_ + 24LL * peak) <= cap) {
-                T.flags |= kSubU;
-                ++nu;
-                sub_lds_u_ = std::max(sub_lds_u_, 24 * peak);
-                for (int v : all) {
-                    snodes[fidx[v]].slot = slot[v] >= 0 ? ubase + 3 * slot[v] : -1;
-                    // v's pull lists name its children's update entries (all inside the subtree)
-                    const long long e1 = ell_off[v] + (long long)(p[v] + nb[v]) * ell_w[v];
-                    for (long long i = ell_off[v]; i < e1; ++i) {
-                        const long long e = ell[i];
-                        if (e < 0) continue;
-                        long long to = -1;
-                        for (int c : kids[v])
-                            if (e >= uoff[c] && e < uoff[c] + 3LL * nb[c]) { to = ubase + 3LL * slot[c] + (e - uoff[c]); break; }
-                        if (to < 0) throw Error(ERR_STATE, "DirectSolver: internal error: a pull outside its fused subtree");
-                        ell[i] = to;
-                    }
-                }
-            }
-        }
-        if (want_x) {
-            // the x rows a boundary inside the subtree can name: the columns of its inner supernodes
-            // (a boundary names ancestors only, so leaves' columns never) and the root's boundary
-            // (every entry leaving the subtree is one of them: fill-path property of the
-            // elimination tree; checked, else the subtree keeps HBM)
-            std::vector<std::pair<int, int>> inner;   // (first column, supernode), sorted
-            int rows = 0;
-            for (int v : all)
-                if (!kids[v].empty()) { inner.emplace_back(beg[v], v); rows += p[v]; }
-            std::sort(inner.begin(), inner.end());
-            const std::vector<int>& rb = F.bnd[rt];
-            const int nxg = (int)rb.size();
-            if ((long long)KS * (sub_lds_b_ + 24LL * (rows + nxg)) <= cap) {
-                std::vector<int> xo(inner.size());
-                for (size_t k = 0, r = 0; k < inner.size(); r += p[inner[k].second], ++k) xo[k] = xbase + 3 * (int)r;
-                std::vector<std::pair<int, int>> rw;
-                bool ok = true;
-                for (int v : all) {
-                    for (int a = 0; a < nb[v] && ok; ++a) {
-                        const int i = bnd[bnd_off[v] + a];
-                        auto in = std::upper_bound(inner.begin(), inner.end(), std::make_pair(i, INT32_MAX));
-                        int o = -1;
-                        if (in != inner.begin()) {
-                            --in;
-                            const int w = in->second;
-                            if (i < beg[w] + p[w]) o = xo[in - inner.begin()] + 3 * (i - beg[w]);
-                        }
-                        if (o < 0) {
-                            auto it = std::lower_bound(rb.begin(), rb.end(), i);
-                            if (it == rb.end() || *it != i) { ok = false; break; }
-                            o = xbase + 3 * (rows + (int)(it - rb.begin()));
-                        }
-                        rw.emplace_back(bnd_off[v] + a, o);
-                    }
-                    if (!ok) break;
-                }
-                if (ok) {
-                    for (const auto& q : rw) bnd[q.first] = q.second;
-                    for (size_t k = 0; k < inner.size(); ++k) snodes[bidx[inner[k].second]].xo = xo[k];
-                    T.flags |= kSubX;
-                    ++nx;
-                    T.xst = xbase + 3 * rows;
-                    T.nxg = nxg;
-                    T.xg_off = (int)xg.size();
-                    xg.insert(xg.end(), rb.begin(), rb.end());
-                    sub_lds_x_ = std::max(sub_lds_x_, 24 * (rows + nxg));
-                }
-            }
-        }
+// knobs, plan (solve_plan.cpp), then the upload: nothing about the solve is decided here
+void DirectSolver::build(const SupernodalFactor& F, hipStream_t s, const std::vector<int>* node_part, int my_part,
+                         int top_beg, Comm* comm, int max_sets, bool wide, int wave_p, int wave_r) {
+    const SolveKnobs knobs = SolveKnobs::from_env();
+    SolvePlanIn in;
+    in.F = &F; in.node_part = node_part; in.my_part = my_part; in.top_beg = top_beg;
+    if (comm) { in.comm_size = comm->size(); in.comm_rank = comm->rank(); }
+    in.max_sets = max_sets; in.wide = wide; in.wave_p = wave_p; in.wave_r = wave_r;
+    in.default_branches = default_branches;
+    pl_ = plan_solve(in, knobs);
+    SolvePlan& P = pl_;
+    comm_ = P.partitioned ? comm : nullptr;
+    const int KS = P.KS, n_sub = (int)P.strees.size();
+    // fused subtrees
+    sub_xg_.upload(P.xg, s);
+    sub_nodes_.upload(P.snodes, s);
+    sub_levels_.upload(P.slevels, s);
+    sub_trees_.upload(P.strees, s);
+    sub_items_.upload(P.items, s);
+    sub_items2_.upload(P.items2, s);
+    sub_timing_ = P.sub_timing;
+    if (sub_timing_ > 0 && n_sub > 0) { sub_clk_.alloc(2 * 64 * (size_t)n_sub); sub_clk_.zero(s); }
+    if (P.cut_height + 1 > 21) sub_timing_ = 0;   // 64 clock slots per workgroup
+    if (P.nbr > 1) {
+        int dev = 0;
+        AA_HIP(hipStreamGetDevice(s, &dev));
+        for (int b = 0; b < P.nbr; ++b) side_[b].create(dev);
     }
-    if (xg.empty()) xg.push_back(0);
-    sub_xg_.upload(xg, s);
-    if (stats)
-        std::fprintf(stderr, "[solve] fused subtrees in LDS: update vectors %d / %zu (%d B), x rows %d / %zu (%d B), per 3 columns\n",
-                     nu, sub_all.size(), sub_lds_u_, nx, sub_all.size(), sub_lds_x_);
-}
-
-// Branches: the supernodes that head the B heaviest disjoint subtrees (found by expanding the
-// heaviest non-fused node of the frontier, from the roots down, until there are B of them;
-// expanded nodes form the top), dealt to B streams by decreasing factor bytes (each to the
-// lightest stream so far). Every launch of a sweep below the top then runs once per branch on its
-// own stream: a branch's next level starts while another branch's level still drains, so the
-// levels' ramp and tail overlap instead of adding up. Same tasks, tiles and sums: bit-identical.
-void DirectSolver::plan_branches(const SupernodalFactor& F, const std::vector<char>& inc, const std::vector<char>& fused,
-                                 const std::vector<std::vector<int>>& kids, const std::vector<int>& p,
-                                 const std::vector<int>& nb, bool stats) {
-    nbr_ = 1;
-    brn_.assign(nn_, 0);
-    const char* er = std::getenv("AA_SOLVE_BRANCHES_REJECT");
-    branch_reject_ = er && er[0] == '1';
-    const char* e = std::getenv("AA_SOLVE_BRANCHES");
-    const char* st = std::getenv("AA_SOLVE_STREAM");
-    const int want = std::max(1, std::min(kMaxBranches, e ? std::atoi(e) : default_branches));
-    if (want < 2 || (st && st[0] == '1')) return;
-    // subtree weights (factor entries), children before parents by height
-    std::vector<int> order;
-    for (int sn = 0; sn < nn_; ++sn) if (inc[sn]) order.push_back(sn);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return F.height[a] < F.height[b]; });
-    std::vector<double> wt(nn_, 0.0);
-    for (int sn : order) {
-        wt[sn] += 0.5 * p[sn] * (p[sn] + 1.0) + (double)p[sn] * nb[sn];
-        if (F.parent[sn] >= 0 && inc[F.parent[sn]]) wt[F.parent[sn]] += wt[sn];
+    if (P.top_sn >= 0) {
+        top_task_d_.upload(std::vector<Task>{P.top_task}, s);
+        top_f_.alloc(3 * (size_t)KS * P.top_p);
+        top_x_.alloc(3 * (size_t)KS * P.top_p);
     }
-    std::vector<int> front, top;
-    for (int sn : order) if (F.parent[sn] < 0 || !inc[F.parent[sn]]) front.push_back(sn);
-    while ((int)front.size() < want) {
-        int best = -1;
-        for (size_t k = 0; k < front.size(); ++k) {
-            const int v = front[k];
-            if (fused[v] || kids[v].empty()) continue;
-            if (best < 0 || wt[v] > wt[front[best]]) best = (int)k;
-        }
-        if (best < 0) break;
-        const int v = front[best];
-        front.erase(front.begin() + best);
-        top.push_back(v);
-        for (int c : kids[v]) front.push_back(c);
+    bnd_.upload(P.bnd, s);
+    ell_.upload(P.ell, s);
+    upload_factor(F, s);
+    if (P.stream_plan) {
+        forder_.upload(P.forder.empty() ? std::vector<int>{0} : P.forder, s);
+        border_.upload(P.border.empty() ? std::vector<int>{0} : P.border, s);
+        bndx_.upload(P.bndx.empty() ? std::vector<int>{-1} : P.bndx, s);
+        sync_.alloc((size_t)P.n_heads + 2 * (size_t)P.nn);
+        sync_.zero(s);
+        Xs_.alloc(std::max<long long>(3 * KS * P.xs_rows, 3));
     }
-    if (front.size() < 2) return;
-    const int B = std::min<int>(want, (int)front.size());
-    std::sort(front.begin(), front.end(), [&](int a, int b) { return wt[a] > wt[b]; });
-    std::vector<double> load(B, 0.0);
-    for (int v : front) {
-        const int b = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        load[b] += wt[v];
-        std::vector<int> st2{v};
-        while (!st2.empty()) {
-            const int u = st2.back();
-            st2.pop_back();
-            brn_[u] = b;
-            for (int c : kids[u]) st2.push_back(c);
-        }
+    tasks_.upload(P.tasks, s);
+    btiles_.upload(P.btiles, s);
+    ftiles_.upload(P.ftiles, s);
+    freds_.upload(P.freds, s);
+    fcnt_.alloc(std::max<size_t>(P.freds.size(), 1)); fcnt_.zero(s);
+    bcnt_.alloc(std::max<size_t>(P.breds.size(), 1)); bcnt_.zero(s);
+    breds_.upload(P.breds, s);
+    bpart_.alloc(std::max<long long>(KS * P.part_doubles, 3));
+    Y_.alloc(3 * KS * (size_t)P.n);
+    U_.alloc(std::max<long long>(KS * P.u_doubles, 3));
+    if (std::max(P.sub_lds_bytes(KS, true), P.sub_lds_bytes(KS, false)) > 64 * 1024) {
+        raise_sub_lds<3, false>(); raise_sub_lds<6, false>(); raise_sub_lds<3, true>(); raise_sub_lds<6, true>();
     }
-    for (int v : top) brn_[v] = B;
-    nbr_ = B;
-    if (stats) {
-        double tw = 0;
-        for (int v : top) tw += 0.5 * p[v] * (p[v] + 1.0) + (double)p[v] * nb[v];
-        std::fprintf(stderr, "[solve] branches: %d streams, %zu top supernodes (%.1f MB/sweep), branch MB/sweep:", B, top.size(),
-                     8e-6 * tw);
-        for (double l : load) std::fprintf(stderr, " %.1f", 8e-6 * l);
-        std::fprintf(stderr, "\n");
+    if (KS * P.max_lds > 64 * 1024) {   // large fronts
+        raise_row_lds<3, false>(); raise_row_lds<6, false>(); raise_row_lds<3, true>(); raise_row_lds<6, true>();
     }
+    AA_HIP(hipStreamSynchronize(s));
+    // what only the device reads from here on
+    drop(P.bnd); drop(P.ell); drop(P.snodes); drop(P.slevels); drop(P.items); drop(P.items2); drop(P.xg);
+    drop(P.tasks); drop(P.ftiles); drop(P.freds); drop(P.btiles); drop(P.breds); drop(P.fwid); drop(P.bwid);
+    drop(P.forder); drop(P.border); drop(P.bndx);
 }
 
 void DirectSolver::solve(const double* b, double* x, const Ctrl* ctrl, int gate_reject, hipStream_t s) {
@@ -2144,7 +1301,7 @@ void DirectSolver::solve(const double* b, double* x, const Ctrl* ctrl, int gate_
 
 void DirectSolver::solve2(const double* b0, double* x0, const double* b1, double* x1, const Ctrl* ctrl, int gate_reject,
                           hipStream_t s) {
-    if (max_sets_ < 2) throw Error(ERR_STATE, "DirectSolver::solve2 needs build(..., max_sets = 2)");
+    if (pl_.max_sets < 2) throw Error(ERR_STATE, "DirectSolver::solve2 needs build(..., max_sets = 2)");
     solve_nr<6>(b0, x0, b1, x1, ctrl, gate_reject, s);
 }
 
@@ -2153,12 +1310,9 @@ void DirectSolver::solve2(const double* b0, double* x0, const double* b1, double
 template <int NR>
 void DirectSolver::launch_ftiles(int w, int count, int first, const double* b0, const double* b1, int ext_off,
                                  const Ctrl* ctrl, int gate_reject, hipStream_t s) {
-    if (packed_) {
-        auto kf = w == 256 ? (nt_ ? k_fwd_ptile<NR, AA_FWD_CH, 256, AA_TILE_DEPTH, false, true> : k_fwd_ptile<NR, AA_FWD_CH, 256, AA_TILE_DEPTH, false, false>)
-                  : w == 128 ? (nt_ ? k_fwd_ptile<NR, AA_FWD_CH, 128, AA_TILE_DEPTH, false, true> : k_fwd_ptile<NR, AA_FWD_CH, 128, AA_TILE_DEPTH, false, false>)
-                             : (nt_ ? k_fwd_ptile<NR, AA_FWD_CH, 64, AA_TILE_DEPTH, false, true> : k_fwd_ptile<NR, AA_FWD_CH, 64, AA_TILE_DEPTH, false, false>);
-        hipLaunchKernelGGL(kf, dim3(count), dim3(256), 0, s, ftiles_.p, first, Gt_.p, ell_.p, b0, b1, bpart_.p, freds_.p,
-                           fcnt_.p, Y_.p, U_.p, ctrl, gate_reject, ext_off, nullptr, nullptr, 0);
+    if (pl_.packed) {
+        hipLaunchKernelGGL((fwd_ptile<NR, false>(w, pl_.nt)), dim3(count), dim3(256), 0, s, ftiles_.p, first, Gt_.p, ell_.p, b0,
+                           b1, bpart_.p, freds_.p, fcnt_.p, Y_.p, U_.p, ctrl, gate_reject, ext_off, nullptr, nullptr, 0);
     } else {
         auto kf = w == 256 ? k_fwd_tile<NR, AA_FWD_CH, 256> : (w == 128 ? k_fwd_tile<NR, AA_FWD_CH, 128> : k_fwd_tile<NR, AA_FWD_CH, 64>);
         hipLaunchKernelGGL(kf, dim3(count), dim3(256), 0, s, ftiles_.p, first, Gc_.p, ell_.p, b0, b1, bpart_.p, freds_.p,
@@ -2168,12 +1322,9 @@ void DirectSolver::launch_ftiles(int w, int count, int first, const double* b0, 
 template <int NR>
 void DirectSolver::launch_btiles(int w, int count, int first, double* x0, double* x1, int ext_off, const Ctrl* ctrl,
                                  int gate_reject, hipStream_t s) {
-    if (packed_) {
-        auto kb = w == 256 ? (nt_ ? k_bwd_ptile<NR, AA_BWD_CH, 256, AA_TILE_DEPTH, false, true> : k_bwd_ptile<NR, AA_BWD_CH, 256, AA_TILE_DEPTH, false, false>)
-                  : w == 128 ? (nt_ ? k_bwd_ptile<NR, AA_BWD_CH, 128, AA_TILE_DEPTH, false, true> : k_bwd_ptile<NR, AA_BWD_CH, 128, AA_TILE_DEPTH, false, false>)
-                             : (nt_ ? k_bwd_ptile<NR, AA_BWD_CH, 64, AA_TILE_DEPTH, false, true> : k_bwd_ptile<NR, AA_BWD_CH, 64, AA_TILE_DEPTH, false, false>);
-        hipLaunchKernelGGL(kb, dim3(count), dim3(256), 0, s, btiles_.p, first, Gt_.p, bnd_.p, Y_.p, x0, x1, bpart_.p,
-                           breds_.p, bcnt_.p, ctrl, gate_reject, ext_off, nullptr, nullptr, 0, nullptr, nullptr);
+    if (pl_.packed) {
+        hipLaunchKernelGGL((bwd_ptile<NR, false>(w, pl_.nt)), dim3(count), dim3(256), 0, s, btiles_.p, first, Gt_.p, bnd_.p, Y_.p,
+                           x0, x1, bpart_.p, breds_.p, bcnt_.p, ctrl, gate_reject, ext_off, nullptr, nullptr, 0, nullptr, nullptr);
     } else {
         auto kb = w == 256 ? k_bwd_tile<NR, AA_BWD_CH, 256> : (w == 128 ? k_bwd_tile<NR, AA_BWD_CH, 128> : k_bwd_tile<NR, AA_BWD_CH, 64>);
         hipLaunchKernelGGL(kb, dim3(count), dim3(256), 0, s, btiles_.p, first, Gr_.p, bnd_.p, Y_.p, x0, x1, bpart_.p,
@@ -2185,52 +1336,48 @@ void DirectSolver::launch_btiles(int w, int count, int first, double* x0, double
 template <int NR>
 void DirectSolver::launch_fstream(const Stream& S, const double* b0, const double* b1, const Ctrl* ctrl, int gate_reject,
                                   hipStream_t s) {
-    const int w = levels_[S.l0].ftw;
-    auto kf = w == 256 ? (nt_ ? k_fwd_ptile<NR, AA_FWD_CH, 256, AA_TILE_DEPTH, true, true> : k_fwd_ptile<NR, AA_FWD_CH, 256, AA_TILE_DEPTH, true, false>)
-                  : w == 128 ? (nt_ ? k_fwd_ptile<NR, AA_FWD_CH, 128, AA_TILE_DEPTH, true, true> : k_fwd_ptile<NR, AA_FWD_CH, 128, AA_TILE_DEPTH, true, false>)
-                             : (nt_ ? k_fwd_ptile<NR, AA_FWD_CH, 64, AA_TILE_DEPTH, true, true> : k_fwd_ptile<NR, AA_FWD_CH, 64, AA_TILE_DEPTH, true, false>);
-    hipLaunchKernelGGL(kf, dim3(S.count), dim3(256), 0, s, ftiles_.p, S.first, Gt_.p, ell_.p, b0, b1, bpart_.p, freds_.p,
-                       fcnt_.p, Y_.p, U_.p, ctrl, gate_reject, 0, forder_.p, sync_.p, S.head);
+    hipLaunchKernelGGL((fwd_ptile<NR, true>(pl_.levels[S.l0].ftw, pl_.nt)), dim3(S.count), dim3(256), 0, s, ftiles_.p, S.first,
+                       Gt_.p, ell_.p, b0, b1, bpart_.p, freds_.p, fcnt_.p, Y_.p, U_.p, ctrl, gate_reject, 0, forder_.p, sync_.p,
+                       S.head);
 }
 template <int NR>
 void DirectSolver::launch_bstream(const Stream& S, double* x0, double* x1, const Ctrl* ctrl, int gate_reject,
                                   hipStream_t s) {
-    const int w = levels_[S.l0].btw;
-    auto kb = w == 256 ? (nt_ ? k_bwd_ptile<NR, AA_BWD_CH, 256, AA_TILE_DEPTH, true, true> : k_bwd_ptile<NR, AA_BWD_CH, 256, AA_TILE_DEPTH, true, false>)
-                  : w == 128 ? (nt_ ? k_bwd_ptile<NR, AA_BWD_CH, 128, AA_TILE_DEPTH, true, true> : k_bwd_ptile<NR, AA_BWD_CH, 128, AA_TILE_DEPTH, true, false>)
-                             : (nt_ ? k_bwd_ptile<NR, AA_BWD_CH, 64, AA_TILE_DEPTH, true, true> : k_bwd_ptile<NR, AA_BWD_CH, 64, AA_TILE_DEPTH, true, false>);
-    hipLaunchKernelGGL(kb, dim3(S.count), dim3(256), 0, s, btiles_.p, S.first, Gt_.p, bnd_.p, Y_.p, x0, x1, bpart_.p,
-                       breds_.p, bcnt_.p, ctrl, gate_reject, 0, border_.p, sync_.p, S.head, bndx_.p, Xs_.p);
+    hipLaunchKernelGGL((bwd_ptile<NR, true>(pl_.levels[S.l0].btw, pl_.nt)), dim3(S.count), dim3(256), 0, s, btiles_.p, S.first,
+                       Gt_.p, bnd_.p, Y_.p, x0, x1, bpart_.p, breds_.p, bcnt_.p, ctrl, gate_reject, 0, border_.p, sync_.p, S.head,
+                       bndx_.p, Xs_.p);
 }
 
 template <int NR>
 void DirectSolver::solve_nr(const double* b0, double* x0, const double* b1, double* x1, const Ctrl* ctrl,
                             int gate_reject, hipStream_t s) {
     constexpr int K = NR / 3;
+    const SolvePlan& P = pl_;
+    const int n_sub = (int)P.strees.size();
     const Task* T = tasks_.p;
     // AA_SUB_TIMING: phase clocks of the fused subtrees, printed for the first solves (eager only)
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     AA_HIP(hipStreamIsCapturing(s, &cst));
-    const bool clk_on = sub_timing_ > 0 && cst == hipStreamCaptureStatusNone && n_sub_ > 0;
-    const int noff_f = (K * (sub_lds_f_ + sub_lds_u_) + 15) / 16 * 16, noff_b = (K * (sub_lds_b_ + sub_lds_x_) + 15) / 16 * 16;
+    const bool clk_on = sub_timing_ > 0 && cst == hipStreamCaptureStatusNone && n_sub > 0;
+    const int noff_f = (K * (P.sub_lds_f + P.sub_lds_u) + 15) / 16 * 16, noff_b = (K * (P.sub_lds_b + P.sub_lds_x) + 15) / 16 * 16;
     // queue heads and dependency counters of the streamed runs start from zero every solve
-    const bool st_on = stream_plan_ && (stream_ || (gate_reject == 1 && stream_gated_));
-    if (st_on) AA_HIP(hipMemsetAsync(sync_.p, 0, sizeof(int) * ((size_t)n_heads_ + 2 * (size_t)nn_), s));
-#define SUBF(BL, T0, NT, ST) hipLaunchKernelGGL((nt_rows_ ? k_fwd_sub<BL, NR, true> : k_fwd_sub<BL, NR, false>), dim3(NT), dim3(BL), sub_lds_bytes(K, true), ST, sub_trees_.p, \
+    const bool st_on = P.stream_plan && (P.stream || (gate_reject == 1 && P.stream_gated));
+    if (st_on) AA_HIP(hipMemsetAsync(sync_.p, 0, sizeof(int) * ((size_t)P.n_heads + 2 * (size_t)P.nn), s));
+#define SUBF(BL, T0, NT, ST) hipLaunchKernelGGL((P.nt_rows ? k_fwd_sub<BL, NR, true> : k_fwd_sub<BL, NR, false>), dim3(NT), dim3(BL), P.sub_lds_bytes(K, true), ST, sub_trees_.p, \
                                     sub_levels_.p, sub_nodes_.p, sub_items_.p, Gc_.p, ell_.p, b0, b1, Y_.p, U_.p, ctrl, gate_reject, \
                                     clk_on ? sub_clk_.p : nullptr, 64, noff_f, T0)
-#define SUBB(BL, T0, NT, ST) hipLaunchKernelGGL((nt_rows_ ? k_bwd_sub<BL, NR, true> : k_bwd_sub<BL, NR, false>), dim3(NT), dim3(BL), sub_lds_bytes(K, false), ST, sub_trees_.p, \
+#define SUBB(BL, T0, NT, ST) hipLaunchKernelGGL((P.nt_rows ? k_bwd_sub<BL, NR, true> : k_bwd_sub<BL, NR, false>), dim3(NT), dim3(BL), P.sub_lds_bytes(K, false), ST, sub_trees_.p, \
                                     sub_levels_.p, sub_nodes_.p, sub_items_.p, sub_items2_.p, Gr_.p, bnd_.p, Y_.p, x0, x1, sub_xg_.p, \
-                                    ctrl, gate_reject, clk_on ? sub_clk_.p + 64 * (size_t)n_sub_ : nullptr, 64, noff_b, T0)
-#define FWD(BL, F0, NC, LDS, ST) hipLaunchKernelGGL((nt_rows_ ? k_fwd<BL, NR, true> : k_fwd<BL, NR, false>), dim3(NC), dim3(BL), LDS, ST, T, F0, Gc_.p, \
+                                    ctrl, gate_reject, clk_on ? sub_clk_.p + 64 * (size_t)n_sub : nullptr, 64, noff_b, T0)
+#define FWD(BL, F0, NC, LDS, ST) hipLaunchKernelGGL((P.nt_rows ? k_fwd<BL, NR, true> : k_fwd<BL, NR, false>), dim3(NC), dim3(BL), LDS, ST, T, F0, Gc_.p, \
                                    ell_.p, b0, b1, Y_.p, U_.p, ctrl, gate_reject)
-#define BWD(BL, F0, NC, LDS, ST) hipLaunchKernelGGL((nt_rows_ ? k_bwd<BL, NR, true> : k_bwd<BL, NR, false>), dim3(NC), dim3(BL), LDS, ST, T, F0, Gr_.p, \
+#define BWD(BL, F0, NC, LDS, ST) hipLaunchKernelGGL((P.nt_rows ? k_bwd<BL, NR, true> : k_bwd<BL, NR, false>), dim3(NC), dim3(BL), LDS, ST, T, F0, Gr_.p, \
                                    bnd_.p, Y_.p, x0, x1, ctrl, gate_reject)
     auto sub_fwd = [&](int t0, int nt, hipStream_t st) {
-        if (nt) switch (sub_block_) { case 1024: SUBF(1024, t0, nt, st); break; case 512: SUBF(512, t0, nt, st); break; default: SUBF(256, t0, nt, st); break; }
+        if (nt) switch (P.sub_block) { case 1024: SUBF(1024, t0, nt, st); break; case 512: SUBF(512, t0, nt, st); break; default: SUBF(256, t0, nt, st); break; }
     };
     auto sub_bwd = [&](int t0, int nt, hipStream_t st) {
-        if (nt) switch (sub_block_) { case 1024: SUBB(1024, t0, nt, st); break; case 512: SUBB(512, t0, nt, st); break; default: SUBB(256, t0, nt, st); break; }
+        if (nt) switch (P.sub_block) { case 1024: SUBB(1024, t0, nt, st); break; case 512: SUBB(512, t0, nt, st); break; default: SUBB(256, t0, nt, st); break; }
     };
     // one level's forward (row tasks, then split-K tiles) / backward launches over a range
     auto lvl_fwd = [&](const Level& L, const BrRange& r, hipStream_t st) {
@@ -2251,7 +1398,7 @@ void DirectSolver::solve_nr(const double* b0, double* x0, const double* b1, doub
 #undef BWD
     // the reject path's gated one-set solve (skipped in most iterations) on one stream unless
     // AA_SOLVE_BRANCHES_REJECT=1: a skipped solve costs its launches, twice the streams twice them
-    const int NB = (gate_reject && !branch_reject_) ? 1 : nbr_;
+    const int NB = (gate_reject && !P.branch_reject) ? 1 : P.nbr;
     if (NB > 1) {
         // branches: fork, each branch's fused subtrees and levels on its stream, join, then the
         // top's levels on s (see plan_branches)
@@ -2259,23 +1406,23 @@ void DirectSolver::solve_nr(const double* b0, double* x0, const double* b1, doub
         for (int b = 1; b < NB; ++b) AA_HIP(hipStreamWaitEvent(side_[b].st, side_[0].fork_f, 0));
         for (int b = 0; b < NB; ++b) {
             hipStream_t st = b ? side_[b].st : s;
-            sub_fwd(sub_rng_[b].first, sub_rng_[b].second, st);
-            for (size_t li = 0; li < levels_.size(); ++li) lvl_fwd(levels_[li], lbr_[li * (NB + 1) + b], st);
+            sub_fwd(P.sub_rng[b].first, P.sub_rng[b].second, st);
+            for (size_t li = 0; li < P.levels.size(); ++li) lvl_fwd(P.levels[li], P.lbr[li * (NB + 1) + b], st);
         }
         for (int b = 1; b < NB; ++b) {
             AA_HIP(hipEventRecord(side_[b].join_f, side_[b].st));
             AA_HIP(hipStreamWaitEvent(s, side_[b].join_f, 0));
         }
-        for (size_t li = 0; li < levels_.size(); ++li) lvl_fwd(levels_[li], lbr_[li * (NB + 1) + NB], s);
+        for (size_t li = 0; li < P.levels.size(); ++li) lvl_fwd(P.levels[li], P.lbr[li * (NB + 1) + NB], s);
     } else {
-        sub_fwd(0, n_sub_, s);
+        sub_fwd(0, n_sub, s);
     }
     size_t fs = 0;
-    for (int li = 0; li < (int)levels_.size() && NB == 1; ++li) {
-        const Level& L = levels_[li];
-        if (st_on && fs < fstreams_.size() && fstreams_[fs].l0 == li) {
-            launch_fstream<NR>(fstreams_[fs], b0, b1, ctrl, gate_reject, s);
-            li = fstreams_[fs++].l1 - 1;
+    for (int li = 0; li < (int)P.levels.size() && NB == 1; ++li) {
+        const Level& L = P.levels[li];
+        if (st_on && fs < P.fstreams.size() && P.fstreams[fs].l0 == li) {
+            launch_fstream<NR>(P.fstreams[fs], b0, b1, ctrl, gate_reject, s);
+            li = P.fstreams[fs++].l1 - 1;
             continue;
         }
         BrRange r;
@@ -2286,38 +1433,38 @@ void DirectSolver::solve_nr(const double* b0, double* x0, const double* b1, doub
     // and in the update vectors); their sum over the GPUs is the full forward result. When the
     // solve is gated off the stale rows are summed too -- harmless, the next forward rewrites
     // them and the backward sweep is gated alike on every GPU.
-    if (top_sn_ >= 0) {
+    if (P.top_sn >= 0) {
         // dense top: sum the front over the GPUs, forward of the own rows, backward products of
         // the own rows into a partial x_top, sum it, scatter it into x
-        const int pt = top_p_;
+        const int pt = P.top_p;
         const unsigned nb = (unsigned)((pt + 255) / 256);
         hipLaunchKernelGGL((k_top_front<NR>), dim3(nb), dim3(256), 0, s, top_task_d_.p, ell_.p, b0, b1, U_.p, top_f_.p,
                            ctrl, gate_reject);
         comm_->allreduce_sum(top_f_.p, top_f_.p, 3 * (size_t)K * pt, s);
         // the tiles address the front / x by global row beg + q: the set-major buffers hold rows
         // from beg on (ext_off)
-        const int eo = top_task_.beg;
-        if (top_ft_count_)
-            launch_ftiles<NR>(top_ftw_, top_ft_count_, top_ft_first_, top_f_.p, top_f_.p + 3 * (size_t)pt, eo, ctrl,
+        const int eo = P.top_task.beg;
+        if (P.top_ft_count)
+            launch_ftiles<NR>(P.top_ftw, P.top_ft_count, P.top_ft_first, top_f_.p, top_f_.p + 3 * (size_t)pt, eo, ctrl,
                               gate_reject, s);
         AA_HIP(hipMemsetAsync(top_x_.p, 0, sizeof(double) * 3 * (size_t)K * pt, s));
-        if (top_bt_count_)
-            launch_btiles<NR>(top_btw_, top_bt_count_, top_bt_first_, top_x_.p, top_x_.p + 3 * (size_t)pt, eo, ctrl,
+        if (P.top_bt_count)
+            launch_btiles<NR>(P.top_btw, P.top_bt_count, P.top_bt_first, top_x_.p, top_x_.p + 3 * (size_t)pt, eo, ctrl,
                               gate_reject, s);
         comm_->allreduce_sum(top_x_.p, top_x_.p, 3 * (size_t)K * pt, s);
         hipLaunchKernelGGL((k_top_scatter<NR>), dim3(nb), dim3(256), 0, s, top_task_d_.p, top_x_.p, x0, x1, ctrl,
                            gate_reject);
-    } else if (comm_ && top_beg_ < n_) {
-        comm_->allreduce_sum(Y_.p + NR * (size_t)top_beg_, Y_.p + NR * (size_t)top_beg_, NR * (size_t)(n_ - top_beg_), s);
+    } else if (comm_ && P.top_beg < P.n) {
+        comm_->allreduce_sum(Y_.p + NR * (size_t)P.top_beg, Y_.p + NR * (size_t)P.top_beg, NR * (size_t)(P.n - P.top_beg), s);
     }
     if (NB > 1) {   // the backward mirrors the forward: the top first, then the branches
-        for (int li = (int)levels_.size() - 1; li >= 0; --li) lvl_bwd(levels_[li], lbr_[li * (NB + 1) + NB], s);
+        for (int li = (int)P.levels.size() - 1; li >= 0; --li) lvl_bwd(P.levels[li], P.lbr[li * (NB + 1) + NB], s);
         AA_HIP(hipEventRecord(side_[0].fork_b, s));
         for (int b = 1; b < NB; ++b) AA_HIP(hipStreamWaitEvent(side_[b].st, side_[0].fork_b, 0));
         for (int b = 0; b < NB; ++b) {
             hipStream_t st = b ? side_[b].st : s;
-            for (int li = (int)levels_.size() - 1; li >= 0; --li) lvl_bwd(levels_[li], lbr_[li * (NB + 1) + b], st);
-            sub_bwd(sub_rng_[b].first, sub_rng_[b].second, st);
+            for (int li = (int)P.levels.size() - 1; li >= 0; --li) lvl_bwd(P.levels[li], P.lbr[li * (NB + 1) + b], st);
+            sub_bwd(P.sub_rng[b].first, P.sub_rng[b].second, st);
         }
         for (int b = 1; b < NB; ++b) {
             AA_HIP(hipEventRecord(side_[b].join_b, side_[b].st));
@@ -2328,49 +1475,49 @@ void DirectSolver::solve_nr(const double* b0, double* x0, const double* b1, doub
         return;
     }
     size_t bs = 0;
-    for (int li = (int)levels_.size() - 1; li >= 0; --li) {
-        const Level& L = levels_[li];
-        if (st_on && bs < bstreams_.size() && bstreams_[bs].l1 - 1 == li) {
-            launch_bstream<NR>(bstreams_[bs], x0, x1, ctrl, gate_reject, s);
-            li = bstreams_[bs++].l0;
+    for (int li = (int)P.levels.size() - 1; li >= 0; --li) {
+        const Level& L = P.levels[li];
+        if (st_on && bs < P.bstreams.size() && P.bstreams[bs].l1 - 1 == li) {
+            launch_bstream<NR>(P.bstreams[bs], x0, x1, ctrl, gate_reject, s);
+            li = P.bstreams[bs++].l0;
             continue;
         }
         BrRange r;
         r.bwd_first = L.bwd_first; r.bwd_count = L.bwd_count; r.bt_first = L.bt_first; r.bt_count = L.bt_count;
         lvl_bwd(L, r, s);
     }
-    sub_bwd(0, n_sub_, s);
+    sub_bwd(0, n_sub, s);
     AA_CHECK_LAUNCH();
     if (clk_on) {
         --sub_timing_;
         AA_HIP(hipStreamSynchronize(s));
-        std::vector<long long> h(2 * 64 * (size_t)n_sub_);
+        std::vector<long long> h(2 * 64 * (size_t)n_sub);
         AA_HIP(hipMemcpy(h.data(), sub_clk_.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        std::vector<SubTree> tr(n_sub_);
+        std::vector<SubTree> tr(n_sub);
         AA_HIP(hipMemcpy(tr.data(), sub_trees_.p, tr.size() * sizeof(SubTree), hipMemcpyDeviceToHost));
         const int nl = tr[0].nlvl;
         auto show = [&](const char* what, int base, int nph) {   // median / max over workgroups, us (100 MHz)
             std::fprintf(stderr, "[solve] sub timing NR=%d %s:", NR, what);
             for (int q = 1; q <= nph; ++q) {
                 std::vector<double> d;
-                for (int b = 0; b < n_sub_; ++b)
+                for (int b = 0; b < n_sub; ++b)
                     if (tr[b].nlvl == nl) d.push_back(0.01 * (double)(h[(base + b) * 64 + q] - h[(base + b) * 64 + q - 1]));
                 if (d.empty()) continue;
                 std::sort(d.begin(), d.end());
                 std::fprintf(stderr, " %.1f/%.1f", d[d.size() / 2], d.back());
             }
             std::vector<double> tot;
-            for (int b = 0; b < n_sub_; ++b)
+            for (int b = 0; b < n_sub; ++b)
                 if (tr[b].nlvl == nl) tot.push_back(0.01 * (double)(h[(base + b) * 64 + nph] - h[(base + b) * 64]));
             std::sort(tot.begin(), tot.end());
             std::fprintf(stderr, " | total %.1f/%.1f us", tot[tot.size() / 2], tot.back());
             // every workgroup (any level count): start and end against the earliest start
             const int per = nph / nl;
             long long t0 = h[(size_t)base * 64];
-            for (int b = 0; b < n_sub_; ++b) t0 = std::min(t0, h[(size_t)(base + b) * 64]);
+            for (int b = 0; b < n_sub; ++b) t0 = std::min(t0, h[(size_t)(base + b) * 64]);
             std::vector<double> st, en;
             std::map<int, int> by_lvl;
-            for (int b = 0; b < n_sub_; ++b) {
+            for (int b = 0; b < n_sub; ++b) {
                 st.push_back(0.01 * (double)(h[(size_t)(base + b) * 64] - t0));
                 en.push_back(0.01 * (double)(h[(size_t)(base + b) * 64 + per * tr[b].nlvl] - t0));
                 ++by_lvl[tr[b].nlvl];
@@ -2383,7 +1530,7 @@ void DirectSolver::solve_nr(const double* b0, double* x0, const double* b1, doub
             std::fprintf(stderr, "\n");
         };
         show("fwd (assembly, rows per level, bottom-up)", 0, 2 * nl);
-        show("bwd (vector, segments, columns per level, top-down)", n_sub_, 3 * nl);
+        show("bwd (vector, segments, columns per level, top-down)", n_sub, 3 * nl);
     }
 }
 

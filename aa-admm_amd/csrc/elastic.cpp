@@ -687,7 +687,7 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     if (const char* e = std::getenv("AA_COMB_FUSED")) comb_fused_ = e[0] != '0';
     // Z variant + Anderson: the two-set layout whether pipelined or not (same sums, same bits)
     stamp("factor");
-    // the sweeps as two parallel branches (DirectSolver::plan_branches): measured on C4 (one GPU,
+    // the sweeps as two parallel branches (the planner's branches stage, solve_plan.cpp): measured on C4 (one GPU,
     // Z variant) 407-408 -> 412-416 it/s; three or four branches, and the geometry configs, slower
     // 
     solver_.default_branches = (P == 1 && st_.variant == AA_VARIANT_Z) ? 2 : 1;

@@ -10,9 +10,9 @@
 //    all-reduce), and each rank back-substitutes the top and its own part;
 //  * one dense top root (merge_top = true, DirectSolver's default): each rank forward-sweeps its
 //    own part, the top front is summed, each rank computes its row slice of y_top = Linv f_top
-//    (equal triangle areas in blocks of kBlk rows, as DirectSolver::build) and the backward
-//    products of those rows (a partial x_top), x_top is summed, each rank back-substitutes its
-//    own part.
+//    (equal triangle areas in blocks of kBlk rows: aa::top_row_split, the solver's own) and the
+//    backward products of those rows (a partial x_top), x_top is summed, each rank
+//    back-substitutes its own part.
 // The assembled solution must match the unpartitioned solve and A x = b.
 //   g++ -O2 -std=c++17 -fopenmp tests/cpp/part_solve.cpp aa-admm_amd/csrc/spd_direct.cpp
 #include <algorithm>
@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../aa-admm_amd/csrc/solve_plan.hpp"   // top_row_split
 #include "../../aa-admm_amd/csrc/spd_direct.hpp"
 
 namespace {
@@ -49,7 +50,7 @@ struct SumBarrier {   // all-reduce (sum) of equal-length vectors across P threa
 };
 
 // restatement of DirectSolver's dense-top partitioned solve (direct_solve.hip, solve_nr)
-constexpr int kBlk = 8;   // row block of the split (DirectSolver: kFwdRows = 128; small here so every rank gets rows)
+constexpr int kBlk = 8;   // row block of the split (DirectSolver: kTopBlk = 64; small here so every rank gets rows)
 void solve_dense_top(const aa::SupernodalFactor& F, const aa::NdTree& T, int part, int P, std::vector<double>& b,
                      SumBarrier& bar) {
     const int nn = F.n_nodes;
@@ -74,18 +75,9 @@ void solve_dense_top(const aa::SupernodalFactor& F, const aa::NdTree& T, int par
     const int tb = F.beg[top], pt = F.end[top] - tb;
     double* f = b.data() + 3 * (size_t)tb;
     bar.reduce(f, 3 * (size_t)pt);   // the summed top front
-    // this rank's rows: equal triangle areas in kBlk-row blocks
-    const int nblk = (pt + kBlk - 1) / kBlk;
-    const double total = 0.5 * pt * (pt + 1.0);
-    std::vector<int> cut(P + 1, nblk);
-    cut[0] = 0;
-    double acc = 0;
-    for (int bk = 0, r = 1; bk < nblk && r < P; ++bk) {
-        const double r0 = (double)bk * kBlk, r1 = std::min<double>(pt, r0 + kBlk);
-        acc += 0.5 * (r1 * (r1 + 1) - r0 * (r0 + 1));
-        while (r < P && acc >= total * r / P) cut[r++] = bk + 1;
-    }
-    const int a0 = std::min(pt, cut[part] * kBlk), a1 = std::min(pt, cut[part + 1] * kBlk);
+    // this rank's rows: the solver's own split (equal triangle areas in kBlk-row blocks)
+    const std::pair<int, int> own_rows = aa::top_row_split(pt, P, part, kBlk);
+    const int a0 = own_rows.first, a1 = own_rows.second;
     const std::vector<double>& L = F.Linv[top];
     std::vector<double> y(3 * (size_t)pt, 0.0), x(3 * (size_t)pt, 0.0);
     for (int i = a0; i < a1; ++i)

@@ -108,3 +108,22 @@ def test_explicit_tree_factors_and_solves_on_the_host(tmp_path):
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count("TREE_OK") == 5 and r.stdout.count("REFUSED_OK") == 4 and r.stdout.count("ND_OK") == 3
+
+
+def test_solve_plan_invariants_on_the_host(tmp_path):
+    """tests/cpp/solve_plan.cpp: grid systems through nested_dissection -> multifrontal_cholesky ->
+    plan_solve (aa-admm_amd/csrc/solve_plan.cpp, no HIP) for the settings the GPU cases use -- tile
+    widths, packed on / off, streams off / gated / all, branches, one and two sets, the dense top for
+    2 and 3 parts. Per plan: membership, level order, forward / backward coverage, the top's split,
+    branch ranges, the streamed runs' counters and queue order, the fused subtrees' items and LDS
+    offsets, packed offsets; the one-set plan built wide equals the two-set plan."""
+    if not shutil.which("g++"):
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "solve_plan")
+    csrc = os.path.join(REPO, "aa-admm_amd", "csrc")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fopenmp", "-I", csrc, os.path.join(REPO, "tests", "cpp", "solve_plan.cpp"),
+                    os.path.join(csrc, "solve_plan.cpp"), os.path.join(csrc, "spd_direct.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, OMP_NUM_THREADS="2"))
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.count("PLAN_OK") == 1 and "FAIL" not in r.stdout
