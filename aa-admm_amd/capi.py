@@ -27,7 +27,8 @@ EXPORTS = [
     "aa_elastic_add_obstacle", "aa_elastic_add_mesh_obstacle", "aa_elastic_set_mesh_obstacle_pose",
     "aa_elastic_get_mesh_obstacle_pose", "aa_elastic_set_mesh_obstacle_vertices", "aa_elastic_get_mesh_obstacle_vertices",
     "aa_elastic_bind_mesh_obstacle", "aa_elastic_mesh_obstacle_status", "aa_elastic_set_mesh_obstacle_exempt",
-    "aa_elastic_num_obstacles", "aa_elastic_set_obstacle", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
+    "aa_elastic_num_obstacles", "aa_elastic_set_obstacle", "aa_elastic_set_obstacle_friction", "aa_elastic_get_obstacle_friction",
+    "aa_elastic_record_contacts", "aa_elastic_get_contacts", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
     "aa_elastic_num_nodes", "aa_elastic_get_x", "aa_elastic_get_v", "aa_elastic_set_v", "aa_elastic_get_history",
     "aa_elastic_get_times", "aa_elastic_set_iterations", "aa_elastic_set_x",
     "aa_elastic_runtime", "aa_elastic_bench_iterations", "aa_elastic_kernel_stats", "aa_elastic_local_stats",
@@ -39,7 +40,7 @@ EXPORTS = [
     "aa_geom_runtime_info", "aa_geom_closest_points", "aa_geom_bench_iterations", "aa_geom_kernel_stats",
     "aa_test_prox", "aa_test_cod_solve", "aa_test_geom_project", "aa_test_mesh_sdf", "aa_test_collision_prox",
     "aa_test_mesh_sdf_posed", "aa_test_collision_prox_posed", "aa_test_mesh_refit_tables", "aa_test_mesh_sdf_deformed", "aa_test_direct_solve",
-    "aa_test_bound_refit", "aa_test_collision_prox_exempt",
+    "aa_test_bound_refit", "aa_test_collision_prox_exempt", "aa_test_contact_friction",
 ]
 
 # Geometry constraint types (Geometry/Constraint.h) and SPD solver types (SolverCommon.h)
@@ -440,6 +441,36 @@ class Solver:
         p[:len(q)] = q
         _chk(lib().aa_elastic_set_obstacle(self.h, C.c_int(index), C.c_int(kind), _dp(p)))
 
+    def set_obstacle_friction(self, index, mu):
+        """Coulomb friction coefficient of obstacle row `index` of the insertion order (analytic and
+        mesh rows alike; default 0). Before or after initialize, between steps; the step graph is kept.
+        The friction pass runs in a step iff some row has mu > 0 or recording is on."""
+        _chk(lib().aa_elastic_set_obstacle_friction(self.h, C.c_int(index), C.c_double(mu)))
+
+    def obstacle_friction(self, index):
+        mu = C.c_double()
+        _chk(lib().aa_elastic_get_obstacle_friction(self.h, C.c_int(index), C.byref(mu)))
+        return mu.value
+
+    def record_contacts(self, on=True):
+        """Keep the per-term contact records of every later step even with all coefficients 0."""
+        _chk(lib().aa_elastic_record_contacts(self.h, C.c_int(1 if on else 0)))
+
+    def contacts(self):
+        """The last step's collision terms in contact, in term order: dict(node (caller's numbering),
+        obstacle (row), point, normal, push (j = dt^2 f_n / m), slip (rt), scale (s)); empty when
+        the friction pass did not run."""
+        n = C.c_int()
+        _chk(lib().aa_elastic_get_contacts(self.h, C.c_int(0), C.byref(n), None, None, None, None, None, None, None))
+        k = n.value
+        node, obs = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32)
+        pt, nr, sl = np.zeros((max(k, 1), 3)), np.zeros((max(k, 1), 3)), np.zeros((max(k, 1), 3))
+        push, sc = np.zeros(max(k, 1)), np.zeros(max(k, 1))
+        if k:
+            _chk(lib().aa_elastic_get_contacts(self.h, C.c_int(k), C.byref(n), _ip(node), _ip(obs), _dp(pt), _dp(nr), _dp(push),
+                                               _dp(sl), _dp(sc)))
+        return dict(node=node[:k], obstacle=obs[:k], point=pt[:k], normal=nr[:k], push=push[:k], slip=sl[:k], scale=sc[:k])
+
     def set_collisions(self, inds):
         i = np.ascontiguousarray(inds, np.int32).reshape(-1)
         _chk(lib().aa_elastic_set_collisions(self.h, _ip(i), C.c_int(len(i))))
@@ -606,6 +637,11 @@ def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
     for m, nodes in enumerate(getattr(scene, "mesh_obstacle_exempt", None) or []):
         if nodes is not None:
             s.set_mesh_obstacle_exempt(m, nodes)
+    for row, mu in enumerate(getattr(scene, "obstacle_friction", None) or []):   # per row of the insertion order
+        if mu is not None:
+            s.set_obstacle_friction(row, mu)
+    if getattr(scene, "record_contacts", False):
+        s.record_contacts(True)
     return s
 
 
@@ -629,6 +665,11 @@ def run_scene(ctx: Context, scene, n_steps=None, comm=None):
             row = np.asarray(poses, np.float64)[min(k, len(poses)) - 1]
             for m in range(row.shape[0]):
                 s.set_mesh_obstacle_pose(m, row[m, :9].reshape(3, 3), row[m, 9:])
+        moves = getattr(scene, "obstacle_motion", None)
+        if moves:   # moving analytic obstacles: step k runs against entry k - 1 (the last entry holds on)
+            for row, prm in enumerate(moves[min(k, len(moves)) - 1]):
+                if prm is not None:
+                    s.set_obstacle(row, scene.obstacles[row][0], prm)
         shapes = getattr(scene, "mesh_obstacle_vertices", None)
         if shapes:   # deforming obstacles: step k runs against entry k - 1 (the last entry holds on)
             for m, V in enumerate(shapes[min(k, len(shapes)) - 1]):
@@ -986,6 +1027,69 @@ def hook_collision_prox_exempt(ctx: Context, obstacles, meshes, Q, q_nodes, exem
                                              C.c_int(len(meshes)), None if pp is None else _dp(pp), _dp(q), _ip(qn),
                                              C.c_int(q.shape[0]), _ip(eptr), _ip(enodes), _dp(out)))
     return out
+
+
+def hook_contact_friction(ctx: Context, obstacles, obstacles_prev, mu, meshes, x_old, x_new, u, w, m, penalty, dt,
+                          q_nodes=None, pinned=None, exempt=None, poses=None, poses_prev=None, mesh_still=None):
+    """The friction pass's device function (aa_test_contact_friction) on n queries. obstacles /
+    obstacles_prev: (type, params) rows now and during the previous step (a mesh as (AA_OBS_MESH,
+    [k]) naming meshes[k] = (V, F)), mu one coefficient per row; poses / poses_prev: per mesh (R, t),
+    12 doubles or None; mesh_still: per mesh, True = no displacement is derived for it. Per query
+    x_old, x_new, u (n, 3), w, m (n,), the exemption node id and a pinned flag. Returns dict(x, hit,
+    row, point, normal, push, slip, scale)."""
+    def rows_of(obs):
+        rows = np.zeros((max(len(obs), 1), 8))
+        for k, (kind, prm) in enumerate(obs):
+            a = np.asarray(prm, np.float64).reshape(-1)
+            rows[k, 0] = kind
+            rows[k, 1:1 + len(a)] = a
+        return rows
+    if len(obstacles_prev) != len(obstacles) or len(mu) != len(obstacles):
+        raise ValueError("hook_contact_friction: one previous row and one coefficient per obstacle row")
+    rows, rows_prev = rows_of(obstacles), rows_of(obstacles_prev)
+    mus = np.ascontiguousarray(np.concatenate([np.asarray(mu, np.float64).reshape(-1), np.zeros(1)]))
+    vs = [np.ascontiguousarray(V, np.float64).reshape(-1, 3) for V, _ in meshes]
+    fs = [np.ascontiguousarray(F, np.int32).reshape(-1, 3) for _, F in meshes]
+    vptr = np.concatenate([[0], np.cumsum([len(v) for v in vs])]).astype(np.int32)
+    fptr = np.concatenate([[0], np.cumsum([len(f) for f in fs])]).astype(np.int32)
+    vv = np.ascontiguousarray(np.concatenate(vs) if vs else np.zeros((1, 3)))
+    ff = np.ascontiguousarray(np.concatenate(fs) if fs else np.zeros((1, 3), np.int32))
+    xo = np.ascontiguousarray(x_old, np.float64).reshape(-1, 3)
+    xn = np.ascontiguousarray(x_new, np.float64).reshape(-1, 3)
+    uu = np.ascontiguousarray(u, np.float64).reshape(-1, 3)
+    n = len(xn)
+    ww = np.ascontiguousarray(np.broadcast_to(np.asarray(w, np.float64), (n,)))
+    mm = np.ascontiguousarray(np.broadcast_to(np.asarray(m, np.float64), (n,)))
+    qn = np.ascontiguousarray(np.zeros(n) if q_nodes is None else q_nodes, np.int32).reshape(-1)
+    pin = np.ascontiguousarray(np.zeros(n) if pinned is None else pinned, np.uint8).reshape(-1)
+    if not (len(xo) == len(uu) == len(qn) == len(pin) == n):
+        raise ValueError("hook_contact_friction: the per-query arrays differ in length")
+    lists = [np.asarray([] if e is None else e, np.int32).reshape(-1) for e in (exempt or [None] * len(meshes))]
+    if len(lists) != len(meshes):
+        raise ValueError("hook_contact_friction: one exempt list (or None) per mesh")
+    eptr = np.concatenate([[0], np.cumsum([len(e) for e in lists])]).astype(np.int32)
+    enodes = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, np.int32)]), np.int32)
+
+    def pose_rows(poses):
+        pp = np.full((max(len(meshes), 1), 12), np.nan)   # a row of NaNs: that mesh unposed
+        for k, p in enumerate(poses or []):
+            if p is not None:
+                pp[k] = _pose_arg(p)
+        return pp
+    pp, pq = pose_rows(poses), pose_rows(poses_prev)
+    still = np.ascontiguousarray(np.zeros(max(len(meshes), 1)) if mesh_still is None else
+                                 np.concatenate([np.asarray(mesh_still, np.float64).reshape(-1), np.zeros(1)]), np.uint8)
+    _ub = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte))
+    k1 = max(n, 1)
+    x, hit, row = np.zeros((k1, 3)), np.zeros(k1, np.int32), np.zeros(k1, np.int32)
+    pt, nr, sl, push, sc = np.zeros((k1, 3)), np.zeros((k1, 3)), np.zeros((k1, 3)), np.zeros(k1), np.zeros(k1)
+    _chk(lib().aa_test_contact_friction(
+        ctx.h, _dp(rows), _dp(rows_prev), _dp(mus), C.c_int(len(obstacles)), _dp(vv), _ip(vptr), _ip(ff), _ip(fptr),
+        C.c_int(len(meshes)), _dp(pp), _dp(pq), _ub(still), _ip(qn), _ub(pin), C.c_int(n), _ip(eptr), _ip(enodes), _dp(xo),
+        _dp(xn), _dp(uu), _dp(ww), _dp(mm), C.c_double(penalty), C.c_double(dt), _dp(x), _ip(hit), _ip(row), _dp(pt), _dp(nr),
+        _dp(push), _dp(sl), _dp(sc)))
+    return dict(x=x[:n], hit=hit[:n].astype(bool), row=row[:n], point=pt[:n], normal=nr[:n], push=push[:n], slip=sl[:n],
+                scale=sc[:n])
 
 
 def hook_mesh_sdf_deformed(ctx: Context, V, F, V_new, Q, pose=None, timings=False):

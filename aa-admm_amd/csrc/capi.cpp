@@ -269,6 +269,33 @@ int aa_elastic_set_obstacle(aa_elastic h, int index, int type, const double* par
     });
 }
 
+int aa_elastic_set_obstacle_friction(aa_elastic h, int index, double mu) {
+    return guarded([&] { NEED(h, "null handle"); h->s->set_obstacle_friction(index, mu); });
+}
+
+int aa_elastic_get_obstacle_friction(aa_elastic h, int index, double* mu) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        NEED(mu, "aa_elastic_get_obstacle_friction: null mu");
+        *mu = h->s->obstacle_friction(index);
+    });
+}
+
+int aa_elastic_record_contacts(aa_elastic h, int on) {
+    return guarded([&] { NEED(h, "null handle"); h->s->record_contacts(on != 0); });
+}
+
+int aa_elastic_get_contacts(aa_elastic h, int cap, int* n, int* node, int* obstacle, double* point3, double* normal3,
+                            double* push, double* slip3, double* scale) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        NEED(n, "aa_elastic_get_contacts: null n");
+        NEED(cap >= 0, "aa_elastic_get_contacts: negative cap");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
+        *n = h->s->contacts(cap, node, obstacle, point3, normal3, push, slip3, scale);
+    });
+}
+
 int aa_elastic_set_collisions(aa_elastic h, const int* inds, int n) {
     return guarded([&] { NEED(h, "null handle"); h->s->set_collisions(inds, n); });
 }
@@ -902,6 +929,110 @@ extern "C" int aa_test_collision_prox_exempt(aa_ctx ctx, const double* obs_rows,
             aa::launch_test_collision_prox(dobs.p, dtab.p, dq.p, n, dout.p, s);
         }
         AA_HIP(hipMemcpyAsync(out3, dout.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+        AA_HIP(hipStreamSynchronize(s));
+    });
+}
+
+extern "C" int aa_test_contact_friction(aa_ctx ctx, const double* obs_rows, const double* obs_rows_prev, const double* mu,
+                                       int n_obs, const double* mesh_verts3, const int* mesh_vert_ptr, const int* mesh_tris3,
+                                       const int* mesh_tri_ptr, int n_meshes, const double* mesh_poses,
+                                       const double* mesh_poses_prev, const unsigned char* mesh_still, const int* q_node,
+                                       const unsigned char* q_pinned, int n, const int* exempt_ptr, const int* exempt_nodes,
+                                       const double* x_old3, const double* x_new3, const double* u3, const double* w,
+                                       const double* m, double penalty, double dt, double* x_out3, int* hit, int* row,
+                                       double* point3, double* normal3, double* push, double* slip3, double* scale) {
+    return with_device_arrays(ctx, [&](hipStream_t s) {
+        const char* who = "aa_test_contact_friction: ";
+        NEED(n >= 0 && n_obs >= 0 && n_obs <= aa::kMaxObstacles && (n_obs == 0 || (obs_rows && obs_rows_prev && mu)),
+             std::string(who) + "bad obstacle arguments");
+        NEED(n_meshes >= 0 && n_meshes <= aa::kMaxMeshObstacles, std::string(who) + "too many mesh obstacles");
+        NEED(n_meshes == 0 || (mesh_verts3 && mesh_vert_ptr && mesh_tris3 && mesh_tri_ptr && exempt_ptr), std::string(who) + "null mesh arrays");
+        NEED(n == 0 || (q_node && q_pinned && x_old3 && x_new3 && u3 && w && m), std::string(who) + "null query arrays");
+        NEED(x_out3 && hit && row && point3 && normal3 && push && slip3 && scale, std::string(who) + "null output");
+        int n_ids = 1;
+        for (int e = 0; e < n; ++e) {
+            NEED(q_node[e] >= 0, std::string(who) + "negative node id");
+            NEED(w[e] > 0.0 && m[e] > 0.0, std::string(who) + "weights and masses must be positive");
+            n_ids = std::max(n_ids, q_node[e] + 1);
+        }
+        for (int k = 0; k < n_meshes; ++k) NEED(exempt_ptr[k + 1] >= exempt_ptr[k], std::string(who) + "bad exempt_ptr");
+        if (n_meshes > 0) {
+            NEED(exempt_ptr[n_meshes] == 0 || exempt_nodes, std::string(who) + "null exempt list");
+            for (int j = 0; j < exempt_ptr[n_meshes]; ++j) {
+                NEED(exempt_nodes[j] >= 0, std::string(who) + "negative node id");
+                n_ids = std::max(n_ids, exempt_nodes[j] + 1);
+            }
+        }
+        std::vector<std::unique_ptr<aa::DevBuf<unsigned char>>> ebufs;
+        std::vector<std::unique_ptr<aa::MeshObsBuffers>> bufs;
+        std::vector<aa::MeshObsDev> table((size_t)aa::kMaxMeshObstacles), prev((size_t)aa::kMaxMeshObstacles);
+        std::vector<unsigned char> still((size_t)aa::kMaxMeshObstacles, 0);
+        auto pose_of = [&](const double* poses, int k) -> const double* {
+            const double* pose = poses ? poses + 12 * (size_t)k : nullptr;
+            if (pose && std::all_of(pose, pose + 12, [](double v) { return std::isnan(v); })) pose = nullptr;
+            if (pose) aa::validate_mesh_pose(pose, who);
+            return pose;
+        };
+        for (int k = 0; k < n_meshes; ++k) {
+            const aa::MeshObstacleHost M = aa::prepare_mesh_obstacle(
+                mesh_verts3 + 3 * (size_t)mesh_vert_ptr[k], mesh_vert_ptr[k + 1] - mesh_vert_ptr[k],
+                mesh_tris3 + 3 * (size_t)mesh_tri_ptr[k], mesh_tri_ptr[k + 1] - mesh_tri_ptr[k]);
+            bufs.push_back(std::make_unique<aa::MeshObsBuffers>());
+            table[k] = bufs.back()->upload(M, s);
+            prev[k] = table[k];
+            aa::apply_mesh_pose(table[k], pose_of(mesh_poses, k));
+            aa::apply_mesh_pose(prev[k], pose_of(mesh_poses_prev, k));
+            still[k] = mesh_still ? mesh_still[k] : 0;
+            if (exempt_ptr[k + 1] > exempt_ptr[k]) {
+                std::vector<unsigned char> bytes((size_t)n_ids, 0);
+                for (int j = exempt_ptr[k]; j < exempt_ptr[k + 1]; ++j) bytes[exempt_nodes[j]] = 1;
+                ebufs.push_back(std::make_unique<aa::DevBuf<unsigned char>>());
+                ebufs.back()->upload(bytes, s);
+                AA_HIP(hipStreamSynchronize(s));
+                table[k].exempt = ebufs.back()->p;
+            }
+        }
+        std::vector<double> h(1 + (size_t)aa::kObsStride * aa::kMaxObstacles, 0.0), hp(h.size(), 0.0), hmu((size_t)aa::kMaxObstacles, 0.0);
+        h[0] = hp[0] = n_obs;
+        for (int k = 0; k < n_obs; ++k) {
+            const double* o = obs_rows + (size_t)aa::kObsStride * k;
+            const double* op = obs_rows_prev + (size_t)aa::kObsStride * k;
+            const int type = (int)o[0];
+            NEED(type >= aa::OBS_FLOOR && type <= aa::OBS_MESH && (int)op[0] == type, std::string(who) + "unknown obstacle type, or one that differs from the previous row's");
+            NEED(type != aa::OBS_MESH || (o[1] >= 0 && o[1] < n_meshes && o[1] == (int)o[1]), std::string(who) + "mesh id out of range");
+            NEED(std::isfinite(mu[k]) && mu[k] >= 0.0, std::string(who) + "the coefficient must be finite and >= 0");
+            std::copy(o, o + aa::kObsStride, h.begin() + 1 + (size_t)aa::kObsStride * k);
+            std::copy(op, op + aa::kObsStride, hp.begin() + 1 + (size_t)aa::kObsStride * k);
+            hmu[k] = mu[k];
+        }
+        const size_t nn = (size_t)std::max(n, 1);
+        aa::DevBuf<aa::MeshObsDev> dtab, dprev;
+        dtab.upload(table, s);
+        dprev.upload(prev, s);
+        aa::DevBuf<unsigned char> dstill, dpin;
+        dstill.upload(still, s);
+        aa::DevBuf<double> dobs, dobsp, dmu, dxo, dxn, du, dw, dm;
+        dobs.upload(h, s); dobsp.upload(hp, s); dmu.upload(hmu, s);
+        aa::DevBuf<int> dnode, dhit(nn), drow(nn);
+        aa::DevBuf<double> dc(3 * nn), dn(3 * nn), dj(nn), drt(3 * nn), ds(nn);
+        if (n > 0) {
+            dpin.upload(q_pinned, (size_t)n, s);
+            dnode.upload(q_node, (size_t)n, s);
+            dxo.upload(x_old3, 3 * (size_t)n, s); dxn.upload(x_new3, 3 * (size_t)n, s); du.upload(u3, 3 * (size_t)n, s);
+            dw.upload(w, (size_t)n, s); dm.upload(m, (size_t)n, s);
+            const aa::FrictionTables T{dobsp.p, dprev.p, dmu.p, dstill.p};
+            const aa::ContactRecDev rec{dhit.p, drow.p, dc.p, dn.p, dj.p, drt.p, ds.p};
+            aa::launch_test_contact_friction(dobs.p, n_meshes > 0 ? dtab.p : nullptr, T, dnode.p, dpin.p, dxo.p, dxn.p, du.p,
+                                             dw.p, dm.p, penalty, dt, n, rec, s);
+            AA_HIP(hipMemcpyAsync(x_out3, dxn.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+            AA_HIP(hipMemcpyAsync(hit, dhit.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+            AA_HIP(hipMemcpyAsync(row, drow.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+            AA_HIP(hipMemcpyAsync(point3, dc.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+            AA_HIP(hipMemcpyAsync(normal3, dn.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+            AA_HIP(hipMemcpyAsync(push, dj.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+            AA_HIP(hipMemcpyAsync(slip3, drt.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+            AA_HIP(hipMemcpyAsync(scale, ds.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+        }
         AA_HIP(hipStreamSynchronize(s));
     });
 }

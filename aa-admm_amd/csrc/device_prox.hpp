@@ -374,5 +374,144 @@ __device__ inline void collision_prox(const double* q, const double* obs, double
     else { out[0] = q[0]; out[1] = q[1]; out[2] = q[2]; }
 }
 
+// collision_prox's walk, statement for statement, which also reports the row that supplied the
+// final (dx, point): contact iff the final dx < 0, then row = that obstacle's index in the shared
+// insertion order and c its point in the world frame. Only the friction pass calls it
+// (contact_friction.hip); collision_prox and the kernels built from it are untouched.
+template <class... M>
+__device__ inline bool collision_contact(const double* q, const double* obs, int& row, double* c, M... meshes) {
+#pragma clang fp contract(off)
+    double best = 1.79769313486231570815e+308;
+    double pt[3] = {0.0, 0.0, 0.0};
+    int at = -1;
+    const int n = obs ? (int)obs[0] : 0;
+    auto sq3 = [](double a, double b, double c) { return (a * a + b * b) + c * c; };
+    for (int k = 0; k < n; ++k) {
+        const double* o = obs + 1 + k * kObsStride;
+        const int type = (int)o[0];
+        double dx, p0, p1, p2;
+        if (type == OBS_FLOOR) {
+            dx = q[1] - o[1];
+            p0 = q[0]; p1 = o[1]; p2 = q[2];
+        } else if (type == OBS_SLIDE_FLOOR) {
+            const double l0 = q[0] - o[1], l1 = q[1] - o[2], l2 = q[2] - o[3];
+            dx = l0 * o[4] + l1 * o[5] + l2 * o[6];
+            p0 = q[0] - dx * o[4]; p1 = q[1] - dx * o[5]; p2 = q[2] - dx * o[6];
+        } else if (type == OBS_SPHERE) {
+            double d0 = q[0] - o[1], d1 = q[1] - o[2], d2 = q[2] - o[3];
+            const double z2 = sq3(d0, d1, d2), nrm = sqrt(z2);
+            dx = nrm - o[4];
+            if (dx > best) continue;
+            if (z2 > 0.0) { d0 /= nrm; d1 /= nrm; d2 /= nrm; }
+            p0 = o[1] + d0 * o[4]; p1 = o[2] + d1 * o[4]; p2 = o[3] + d2 * o[4];
+        } else if (type == OBS_PLANE_HALF_SPHERE) {
+            const double dc = sqrt(sq3(q[0] - o[1], 0.0, q[2] - o[3])) - o[4];
+            if (dc > 0) {
+                dx = q[1] - o[2];
+                p0 = q[0]; p1 = o[2]; p2 = q[2];
+            } else {
+                const double dpl = q[1] - o[2];
+                double d0 = q[0] - o[1], d1 = q[1] - o[2], d2 = q[2] - o[3];
+                const double z2 = sq3(d0, d1, d2), nrm = sqrt(z2);
+                dx = dpl > 0 ? nrm + o[4] : o[4] - nrm;
+                if (dx > best) continue;
+                if (z2 > 0.0) { d0 /= nrm; d1 /= nrm; d2 /= nrm; }
+                p0 = o[1] + d0 * o[4]; p1 = o[2] + d1 * o[4]; p2 = o[3] + d2 * o[4];
+            }
+        } else if (sizeof...(M) != 0 && type == OBS_MESH) {
+            if constexpr (sizeof...(M) != 0) {
+                const MeshObsDev& mo = mesh_table_of(meshes...)[(int)o[1]];
+                if (mesh_exempts(mo, meshes...)) continue;
+                double cm[3];
+                int tri;
+                if (!mesh_signed_distance(mo, q, dx, cm, tri)) continue;
+                best = dx;
+                pt[0] = cm[0]; pt[1] = cm[1]; pt[2] = cm[2];
+                at = k;
+            }
+            continue;
+        } else {
+            double d0 = q[0] - o[1], d1 = q[1] - o[2], d2 = 0.0 - o[3];
+            const double z2 = sq3(d0, d1, d2), nrm = sqrt(z2);
+            dx = nrm - o[4];
+            if (dx > best) continue;
+            if (z2 > 0.0) { d0 /= nrm; d1 /= nrm; d2 /= nrm; }
+            p0 = o[1] + d0 * o[4] + 0.0; p1 = o[2] + d1 * o[4] + 0.0; p2 = o[3] + d2 * o[4] + q[2];
+        }
+        if (dx > best) continue;
+        best = dx;
+        pt[0] = p0; pt[1] = p1; pt[2] = p2;
+        at = k;
+    }
+    row = at;
+    c[0] = pt[0]; c[1] = pt[1]; c[2] = pt[2];
+    return best < 0;
+}
+
+// Coulomb friction of one collision term, applied once per step between the ADMM loop and the
+// finalize pass (contact_friction.hpp states the model). fp64, no contraction, sums left to right.
+// in:  xo / xn the node's position at the step's start / as the step writes it back, u the term's
+//      dual, w its weight, m the node's mass, p the penalty, dt the time step; obs / meshes the
+//      tables now, T the previous ones with the coefficients.
+// out: the record (hit, row, c, n, j, rt, s) and xn moved in place when s != 0. `filter` false
+//      (a pinned node): reported, s = 0.
+struct FrictionRec {
+    int hit, row;
+    double c[3], n[3], j, rt[3], s;
+};
+__device__ inline void contact_friction(const double* xo, double* xn, const double* u, double w, double m, double p,
+                                        double dt, const double* obs, const MeshObsDev* meshes, int node,
+                                        const FrictionTables& T, bool filter, FrictionRec& r) {
+#pragma clang fp contract(off)
+    r.hit = 0; r.row = -1; r.j = 0.0; r.s = 0.0;
+    for (int i = 0; i < 3; ++i) { r.c[i] = 0.0; r.n[i] = 0.0; r.rt[i] = 0.0; }
+    double q[3], c[3];
+    collision_candidate(xn, u, w, q);
+    int row;
+    const bool in = meshes ? collision_contact(q, obs, row, c, meshes, node) : collision_contact(q, obs, row, c);
+    if (!in) return;
+    const double e0 = c[0] - q[0], e1 = c[1] - q[1], e2 = c[2] - q[2];
+    const double l = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+    if (l == 0.0) return;
+    const double n[3] = {e0 / l, e1 / l, e2 / l};
+    const double un = (u[0] * n[0] + u[1] * n[1]) + u[2] * n[2];
+    const double k = (((p * dt) * dt) * w) / m;
+    const double j = un < 0.0 ? k * (-un) : 0.0;
+    // the obstacle's displacement at c between the previous step's state and this one's
+    double g[3] = {0.0, 0.0, 0.0};
+    const double* o = obs + 1 + row * kObsStride;
+    const int type = (int)o[0];
+    const int nprev = (int)T.obs_prev[0];
+    if (type == OBS_MESH) {
+        const int mr = (int)o[1];
+        if (!T.mesh_still[mr]) {
+            double cl[3], cp[3];
+            mesh_to_local(meshes[mr], c, cl);
+            mesh_to_world(T.mesh_prev[mr], cl, cp);
+            for (int i = 0; i < 3; ++i) g[i] = c[i] - cp[i];
+        }
+    } else if (row < nprev) {
+        const double* op = T.obs_prev + 1 + row * kObsStride;
+        if (type == OBS_FLOOR) g[1] = o[1] - op[1];
+        else for (int i = 0; i < 3; ++i) g[i] = o[1 + i] - op[1 + i];
+    }
+    double rel[3];
+    for (int i = 0; i < 3; ++i) rel[i] = (xn[i] - xo[i]) - g[i];
+    const double rn = (rel[0] * n[0] + rel[1] * n[1]) + rel[2] * n[2];
+    double rt[3];
+    for (int i = 0; i < 3; ++i) rt[i] = rel[i] - rn * n[i];
+    const double lt = sqrt((rt[0] * rt[0] + rt[1] * rt[1]) + rt[2] * rt[2]);
+    const double mu = T.mu[row];
+    double s = 0.0;
+    if (filter && !(mu == 0.0 || j == 0.0 || !(lt > 0.0))) {
+        const double a = (mu * j) / lt;
+        s = a < 1.0 ? a : 1.0;
+    }
+    if (s != 0.0)
+        for (int i = 0; i < 3; ++i) xn[i] = xn[i] - s * rt[i];
+    r.hit = 1; r.row = row; r.j = j; r.s = s;
+    for (int i = 0; i < 3; ++i) { r.c[i] = c[i]; r.n[i] = n[i]; r.rt[i] = rt[i]; }
+}
+
 }  // namespace dev
 }  // namespace aa

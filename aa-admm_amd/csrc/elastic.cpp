@@ -24,6 +24,7 @@
 namespace aa {
 
 ElasticSolver::~ElasticSolver() {
+    if (fr_ev0_) { (void)hipEventDestroy(fr_ev0_); (void)hipEventDestroy(fr_ev1_); }
     drop_graph();
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_join_) (void)hipEventDestroy(ev_join_);
@@ -233,6 +234,8 @@ void ElasticSolver::set_mesh_obstacle_vertices(int mesh_id, const double* V3) {
     AA_HIP(hipMemcpyAsync(mesh_dev_.p + mesh_id, &d, sizeof(d), hipMemcpyHostToDevice, s()));
     AA_HIP(hipStreamSynchronize(s()));
     mo.verts.assign(V3, V3 + mo.verts.size());
+    mesh_changed_.resize(meshes_.size(), 0);
+    mesh_changed_[mesh_id] = 1;   // friction: no displacement is derived across a change of shape
 }
 
 int ElasticSolver::mesh_obstacle_vertices(int mesh_id, double* V3) const {
@@ -496,6 +499,8 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     std::fill(v_.begin(), v_.end(), 0.0);
     if (st_.variant == AA_VARIANT_Z && !obstacles_.empty())   // admm_anderson_xzu/src/Solver.cpp:485-489
         throw Error(ERR_ARG, "**Solver::add_obstacle Error: No collisions with LDLT solver");
+    if (comm_ && comm_->size() > 1 && friction_active())
+        throw Error(ERR_ARG, "initialize: obstacle friction or contact recording is on and the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (a rank holds only its part of the collision terms; friction needs one rank)");
     if (comm_ && comm_->size() > 1 && any_bound())
         throw Error(ERR_ARG, "initialize: a mesh obstacle is bound to solver nodes and the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (bound obstacles need one rank)");
     if (st_.variant == AA_VARIANT_Z && !coll_nodes_.empty())
@@ -892,6 +897,8 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     }
     AA_HIP(hipStreamSynchronize(s()));
     initialized_ = true;
+    fr_prev_valid_ = false;
+    fr_ran_ = false;
     upload_obstacles();
     for (int m = 0; m < (int)meshes_.size(); ++m) {   // bindings and exemptions given before the numbering existed
         if (meshes_[m]->bound) {
@@ -1343,7 +1350,144 @@ void ElasticSolver::enqueue_iterations(int iters, bool accel) {
     if (st_.variant != AA_VARIANT_UX && accel && pipe_z_ && iters > 0) enqueue_comb_tail_z(iters);
 }
 
+// Friction (contact_friction.hpp)
+bool ElasticSolver::friction_active() const {
+    if (fr_record_) return true;
+    for (double m : fr_mu_) if (m > 0.0) return true;
+    return false;
+}
+
+void ElasticSolver::set_obstacle_friction(int index, double mu) {
+    if (index < 0 || index >= (int)obstacles_.size())
+        throw Error(ERR_ARG, "set_obstacle_friction: index " + std::to_string(index) + " out of range (" + std::to_string(obstacles_.size()) + " obstacles)");
+    if (!std::isfinite(mu) || mu < 0.0) throw Error(ERR_ARG, "set_obstacle_friction: the coefficient must be finite and >= 0");
+    if (mu > 0.0 && initialized_ && comm_ && comm_->size() > 1)
+        throw Error(ERR_ARG, "set_obstacle_friction: the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (a rank holds only its part of the collision terms; friction needs one rank)");
+    if (fr_mu_.size() < obstacles_.size()) fr_mu_.resize(obstacles_.size(), 0.0);
+    fr_mu_[index] = mu;
+}
+
+double ElasticSolver::obstacle_friction(int index) const {
+    if (index < 0 || index >= (int)obstacles_.size())
+        throw Error(ERR_ARG, "get_obstacle_friction: index " + std::to_string(index) + " out of range (" + std::to_string(obstacles_.size()) + " obstacles)");
+    return index < (int)fr_mu_.size() ? fr_mu_[index] : 0.0;
+}
+
+void ElasticSolver::record_contacts(bool on) {
+    if (on && initialized_ && comm_ && comm_->size() > 1)
+        throw Error(ERR_ARG, "record_contacts: the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (a rank holds only its part of the collision terms; recording needs one rank)");
+    fr_record_ = on;
+}
+
+// The pass, on the pair (u, x) the step writes back: with Anderson in the (u, x) variant the
+// un-accelerated pair of the last iteration (default_u, default_x: du_, dx_), otherwise the
+// current one (u_, xfull_). Everything it reads beside the solver's own tables is uploaded here
+// from host snapshots that outlive the copies.
+void ElasticSolver::friction_enqueue(bool accel) {
+    fr_ran_ = false;
+    fr_count_ = 0;
+    if (!friction_active()) {
+        fr_prev_valid_ = false;
+        std::fill(mesh_changed_.begin(), mesh_changed_.end(), 0);
+        return;
+    }
+    fr_ran_ = true;
+    for (auto& g : groups_) if (g.d.kind == 2) fr_count_ += g.d.count;
+    const int nobs = (int)obstacles_.size(), nmesh = (int)meshes_.size();
+    if (fr_count_ > 0) {
+        if (!fr_prev_valid_) { obs_prev_ = obstacles_; mesh_rows_prev_ = mesh_rows_; }
+        fr_h_obs_.assign(1 + (size_t)kObsStride * kMaxObstacles, 0.0);
+        fr_h_mu_.assign(kMaxObstacles, 0.0);
+        fr_h_mesh_.assign(kMaxMeshObstacles, MeshObsDev{});
+        fr_h_still_.assign(kMaxMeshObstacles, 0);
+        fr_h_obs_[0] = (double)nobs;   // a row added since the last step: its state now
+        for (int k = 0; k < nobs; ++k) {
+            const auto& o = k < (int)obs_prev_.size() ? obs_prev_[k] : obstacles_[k];
+            std::copy(o.begin(), o.end(), fr_h_obs_.begin() + 1 + (size_t)kObsStride * k);
+            fr_h_mu_[k] = k < (int)fr_mu_.size() ? fr_mu_[k] : 0.0;
+        }
+        mesh_changed_.resize(nmesh, 0);
+        for (int m = 0; m < nmesh; ++m) {
+            fr_h_mesh_[m] = m < (int)mesh_rows_prev_.size() ? mesh_rows_prev_[m] : mesh_rows_[m];
+            fr_h_still_[m] = (meshes_[m]->bound || mesh_changed_[m]) ? 1 : 0;
+        }
+        if (!fr_obs_prev_.p) {
+            fr_obs_prev_.alloc(fr_h_obs_.size());
+            fr_mu_dev_.alloc(fr_h_mu_.size());
+            fr_mesh_prev_.alloc(fr_h_mesh_.size());
+            fr_still_.alloc(fr_h_still_.size());
+        }
+        AA_HIP(hipMemcpyAsync(fr_obs_prev_.p, fr_h_obs_.data(), fr_h_obs_.size() * sizeof(double), hipMemcpyHostToDevice, s()));
+        AA_HIP(hipMemcpyAsync(fr_mu_dev_.p, fr_h_mu_.data(), fr_h_mu_.size() * sizeof(double), hipMemcpyHostToDevice, s()));
+        AA_HIP(hipMemcpyAsync(fr_mesh_prev_.p, fr_h_mesh_.data(), fr_h_mesh_.size() * sizeof(MeshObsDev), hipMemcpyHostToDevice, s()));
+        AA_HIP(hipMemcpyAsync(fr_still_.p, fr_h_still_.data(), fr_h_still_.size(), hipMemcpyHostToDevice, s()));
+        if ((int)rec_hit_.n < fr_count_) {
+            rec_hit_.alloc(fr_count_); rec_row_.alloc(fr_count_); rec_j_.alloc(fr_count_); rec_s_.alloc(fr_count_);
+            rec_c_.alloc(3 * (size_t)fr_count_); rec_n_.alloc(3 * (size_t)fr_count_); rec_rt_.alloc(3 * (size_t)fr_count_);
+        }
+        const bool def = st_.variant == AA_VARIANT_UX && accel;
+        double* xsrc = def ? dx_.p : xfull_.p;
+        const double* u = def ? du_.p : u_.p;
+        const FrictionTables T{fr_obs_prev_.p, fr_mesh_prev_.p, fr_mu_dev_.p, fr_still_.p};
+        const ContactRecDev rec{rec_hit_.p, rec_row_.p, rec_c_.p, rec_n_.p, rec_j_.p, rec_rt_.p, rec_s_.p};
+        if (!fr_ev0_) { AA_HIP(hipEventCreate(&fr_ev0_)); AA_HIP(hipEventCreate(&fr_ev1_)); }
+        AA_HIP(hipEventRecord(fr_ev0_, s()));   // kernel_stats("friction"): the pass's device time
+        int off = 0;
+        for (auto& g : groups_) {
+            if (g.d.kind != 2) continue;
+            launch_contact_friction(g.d, xs_.p, xsrc, xfull_.p, u, mass_.p, nf_, st_.penalty, st_.timestep_s, mesh_table(g.d),
+                                    T, rec, off, s());
+            off += g.d.count;
+        }
+        AA_HIP(hipEventRecord(fr_ev1_, s()));
+    }
+    obs_prev_ = obstacles_;
+    mesh_rows_prev_ = mesh_rows_;
+    fr_prev_valid_ = true;
+    std::fill(mesh_changed_.begin(), mesh_changed_.end(), 0);
+}
+
+int ElasticSolver::contacts(int cap, int* node, int* obstacle, double* point3, double* normal3, double* push, double* slip3,
+                            double* scale) {
+    if (!fr_ran_ || fr_count_ == 0) return 0;
+    const size_t n = (size_t)fr_count_;
+    std::vector<int> hit(n), row(n);
+    std::vector<double> c(3 * n), nn(3 * n), j(n), rt(3 * n), sc(n);
+    AA_HIP(hipStreamSynchronize(s()));
+    AA_HIP(hipMemcpy(hit.data(), rec_hit_.p, n * sizeof(int), hipMemcpyDeviceToHost));
+    AA_HIP(hipMemcpy(row.data(), rec_row_.p, n * sizeof(int), hipMemcpyDeviceToHost));
+    AA_HIP(hipMemcpy(c.data(), rec_c_.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+    AA_HIP(hipMemcpy(nn.data(), rec_n_.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+    AA_HIP(hipMemcpy(j.data(), rec_j_.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    AA_HIP(hipMemcpy(rt.data(), rec_rt_.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+    AA_HIP(hipMemcpy(sc.data(), rec_s_.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    int k = 0;
+    size_t e = 0;
+    for (auto& g : groups_) {
+        if (g.d.kind != 2) continue;
+        std::vector<int> idx((size_t)g.d.count);
+        AA_HIP(hipMemcpy(idx.data(), g.idx.p, idx.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int t = 0; t < g.d.count; ++t, ++e) {
+            if (!hit[e]) continue;
+            if (k < cap) {
+                if (node) node[k] = int2node_[idx[t]];
+                if (obstacle) obstacle[k] = row[e];
+                if (push) push[k] = j[e];
+                if (scale) scale[k] = sc[e];
+                for (int i = 0; i < 3; ++i) {
+                    if (point3) point3[3 * (size_t)k + i] = c[3 * e + i];
+                    if (normal3) normal3[3 * (size_t)k + i] = nn[3 * e + i];
+                    if (slip3) slip3[3 * (size_t)k + i] = rt[3 * e + i];
+                }
+            }
+            ++k;
+        }
+    }
+    return k;
+}
+
 void ElasticSolver::epilogue_enqueue(bool accel) {
+    friction_enqueue(accel);
     const double* src = (st_.variant == AA_VARIANT_UX && accel) ? dx_.p : xfull_.p;
     launch_finalize(n_, nf_, src, xfull_.p, xs_.p, vs_.p, st_.timestep_s, s());
 }
@@ -1503,6 +1647,16 @@ double ElasticSolver::bench_iterations(int iters) {
 }
 
 bool ElasticSolver::kernel_stats(const std::string& name, double* avg_ms, double* bytes, int* launches) const {
+    if (name == "friction") {   // the last step's friction pass, by device events
+        if (!fr_ran_ || fr_count_ == 0) return false;
+        float ms = 0;
+        AA_HIP(hipEventSynchronize(fr_ev1_));
+        AA_HIP(hipEventElapsedTime(&ms, fr_ev0_, fr_ev1_));
+        if (avg_ms) *avg_ms = ms;
+        if (bytes) *bytes = 0;
+        if (launches) *launches = 1;
+        return true;
+    }
     auto it = kstats_.find(name);
     if (it == kstats_.end()) return false;
     const KStat& k = it->second;

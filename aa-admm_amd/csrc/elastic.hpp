@@ -10,6 +10,7 @@
 #include "../../include/aa_admm.h"
 #include "comm.hpp"
 #include "common.hpp"
+#include "contact_friction.hpp"
 #include "direct_solve.hpp"
 #include "elastic_kernels.hpp"
 #include "mesh_obstacle.hpp"
@@ -97,6 +98,17 @@ public:
     void set_mesh_obstacle_exempt(int mesh_id, const int* nodes, int n);
     int num_obstacles() const { return (int)obstacles_.size(); }
     void set_obstacle(int index, int type, const double* params);
+    // Coulomb friction against the obstacles (contact_friction.hpp): a coefficient per obstacle row
+    // (index in the shared insertion order; before or after initialize, between steps: the pass is
+    // outside the captured graph, which stays) and the per-term contact records of the last step.
+    // The pass runs in a step iff some row has mu > 0 or recording is on. One rank only.
+    void set_obstacle_friction(int index, double mu);
+    double obstacle_friction(int index) const;
+    void record_contacts(bool on);
+    // the last step's terms in contact, in collision-term order; returns their count (every output
+    // optional, at most cap entries written)
+    int contacts(int cap, int* node, int* obstacle, double* point3, double* normal3, double* push, double* slip3,
+                 double* scale);
     // WindForce (ExplicitForce.hpp:39-47) on the given triangles; returns its id
     int add_wind(const int* tris3, int ntris, const double* dir3);
     void set_wind(int id, const double* dir3);
@@ -179,6 +191,26 @@ private:
     bool any_bound() const { for (auto& m : meshes_) if (m->bound) return true; return false; }
     const MeshObsDev* mesh_table(const GroupDev& d) const { return d.kind == 2 && !meshes_.empty() ? mesh_dev_.p : nullptr; }
     void build_wind(Wind& w);
+    // friction: the coefficients, the obstacle state in force during the previous step (host
+    // snapshots, uploaded before the pass; valid once the pass has run in the step before), the
+    // meshes whose vertices changed since, and the device records
+    std::vector<double> fr_mu_;
+    bool fr_record_ = false, fr_prev_valid_ = false, fr_ran_ = false;
+    int fr_count_ = 0;
+    std::vector<std::array<double, kObsStride>> obs_prev_;
+    std::vector<MeshObsDev> mesh_rows_prev_;
+    std::vector<unsigned char> mesh_changed_;
+    std::vector<double> fr_h_obs_, fr_h_mu_;
+    std::vector<MeshObsDev> fr_h_mesh_;
+    std::vector<unsigned char> fr_h_still_;
+    DevBuf<double> fr_obs_prev_, fr_mu_dev_;
+    DevBuf<MeshObsDev> fr_mesh_prev_;
+    DevBuf<unsigned char> fr_still_;
+    DevBuf<int> rec_hit_, rec_row_;
+    DevBuf<double> rec_c_, rec_n_, rec_j_, rec_rt_, rec_s_;
+    hipEvent_t fr_ev0_ = nullptr, fr_ev1_ = nullptr;   // around the pass (kernel_stats("friction"))
+    bool friction_active() const;
+    void friction_enqueue(bool accel);
     std::vector<int> pin_order_;
     aa_settings st_{};
     bool initialized_ = false;

@@ -44,6 +44,13 @@ struct GroupVar {
 // OBS_MESH (PassiveMesh, :138-178): a triangle-mesh obstacle, parameter 1 = its row in the mesh table
 enum ObsType { OBS_FLOOR = 0, OBS_SLIDE_FLOOR = 1, OBS_SPHERE = 2, OBS_PLANE_HALF_SPHERE = 3, OBS_CYLINDER = 4, OBS_MESH = 5 };
 constexpr int kObsStride = 8, kMaxObstacles = 256;
+// What the friction pass reads beside the tables in force (contact_friction.hpp)
+struct FrictionTables {
+    const double* obs_prev;           // the obstacle table in force during the previous step
+    const MeshObsDev* mesh_prev;      // the mesh table's rows then (R and t are read)
+    const double* mu;                 // [rows] coefficient per obstacle row, shared insertion order
+    const unsigned char* mesh_still;  // [mesh rows] non-zero: g = 0 (vertices changed, bound mesh)
+};
 __host__ __device__ constexpr int ncol_of(int nv) { return nv > 1 ? nv - 1 : 1; }   // 1 vertex: identity reduction
 
 // Device-side control block: residual bookkeeping, reject/done flags, Anderson state.

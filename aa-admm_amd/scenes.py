@@ -113,6 +113,15 @@ class Scene:
     mesh_obstacle_bindings: Optional[list] = None
     mesh_obstacle_exempt: Optional[list] = None
     winds: list = dataclasses.field(default_factory=list)
+    # Coulomb friction: a coefficient (or None) per obstacle row of the insertion order, `obstacles`
+    # first, then `mesh_obstacles` (capi.solver_from_scene); record_contacts keeps the per-term contact
+    # records even with every coefficient 0. None / False = no friction pass, today's scene.
+    obstacle_friction: Optional[list] = None
+    record_contacts: bool = False
+    # moving analytic obstacles: a list over steps, each entry a list over the rows of `obstacles` of
+    # new parameters or None for "leave as is"; step k runs against entry k - 1 and the last entry
+    # holds on (capi.run_scene, with the poses)
+    obstacle_motion: Optional[list] = None
 
     @property
     def rest_x(self) -> np.ndarray:
@@ -571,15 +580,19 @@ def rotation_y(angle: float) -> np.ndarray:
     return np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])
 
 
-def cloth_on_spinning_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15, dtheta=0.05) -> Scene:
+def cloth_on_spinning_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15, dtheta=0.05,
+                            friction=None) -> Scene:
     """Demo of the kinematic mesh obstacle: cloth_on_torus with the torus turning about the y axis
-    by `dtheta` per step (step k runs against the torus turned by k dtheta)."""
+    by `dtheta` per step (step k runs against the torus turned by k dtheta). friction: the torus'
+    Coulomb coefficient -- with it the cloth is carried round; None = no friction pass."""
     sc = cloth_on_torus(nx, ny, iters=iters, aa_m=aa_m, accel=accel, n_steps=n_steps, drop=drop)
     sc.name = "cloth_on_spinning_torus"
     poses = np.zeros((n_steps, 1, 12))
     for k in range(n_steps):
         poses[k, 0, :9] = rotation_y((k + 1) * dtheta).reshape(9)
     sc.mesh_obstacle_poses = poses
+    if friction is not None:
+        sc.obstacle_friction = [friction]
     return sc
 
 
@@ -653,4 +666,71 @@ def cloth_on_soft_block(nx=12, ny=12, *, cells=(3, 2, 3), cell=0.3, E=5e4, nu=0.
     sc.mesh_obstacles = [(bv[surf].copy(), local[faces].astype(np.int32))]
     sc.mesh_obstacle_bindings = [surf]
     sc.collision_idx = np.arange(nb, nb + len(cx), dtype=np.int32)
+    return sc
+
+
+# ----------------------------------------------------------------------------------------
+# friction scenes: a stiff linear tet block on a plane ((u,x) variant, its bottom nodes collision-checked)
+# ----------------------------------------------------------------------------------------
+
+def _block(cells, cell, E, nu):
+    v, t = tet_blocks(*cells)
+    v = v * float(cell)
+    v = v - np.array([0.5 * (v[:, 0].max() + v[:, 0].min()), 0.0, 0.5 * (v[:, 2].max() + v[:, 2].min())])
+    bottom = np.nonzero(v[:, 1] < 1e-3 * cell)[0].astype(np.int32)
+    return v, t, tet_masses(v, t, 1522.0), bottom
+
+
+def block_on_incline(theta_deg=20.0, friction=None, *, cells=(4, 2, 4), cell=0.25, E=1e7, nu=0.3, iters=40, aa_m=5,
+                     accel=1, n_steps=40, dt=1.0 / 60.0, record=True, lift=0.0) -> Scene:
+    """A block laid at rest on a SLIDE_FLOOR through the origin tilted by theta about z: the unit
+    normal is (sin theta, cos theta, 0), downhill is (cos theta, -sin theta, 0). Without friction it
+    slides at g sin theta; with the coefficient `friction` at g (sin theta - mu cos theta), and it
+    stays where it is for mu > tan theta. Obstacle row 0. lift: the block starts that far above
+    the plane (along the normal) instead of on it."""
+    v, t, m, bottom = _block(cells, cell, E, nu)
+    th = np.deg2rad(theta_deg)
+    c, s = np.cos(th), np.sin(th)
+    R = np.array([[c, s, 0.0], [-s, c, 0.0], [0.0, 0.0, 1.0]])   # e_x -> downhill, e_y -> the normal
+    sc = Scene(x=v @ R.T + lift * R[:, 1], masses=m, groups=[ElementGroup(TET, LINEAR, E, nu, t)], pin_idx=np.zeros(0, np.int32),
+               pin_pts=np.zeros((0, 3)), pin_vel=np.zeros((0, 3)), variant=VARIANT_H, dt=dt, iters=iters, aa_m=aa_m,
+               n_steps=n_steps, accel=accel, name="block_on_incline", rest=v)
+    sc.obstacles = [(OBS_SLIDE_FLOOR, (0.0, 0.0, 0.0, s, c, 0.0))] if theta_deg != 0.0 else [(OBS_FLOOR, (0.0,))]
+    sc.collision_idx = bottom
+    sc.obstacle_friction = None if friction is None else [friction]
+    sc.record_contacts = record
+    return sc
+
+
+def block_on_moving_floor(friction=None, *, shift=0.01, cells=(4, 2, 4), cell=0.25, E=1e7, nu=0.3, iters=40, aa_m=5,
+                          accel=1, n_steps=40, dt=1.0 / 60.0, record=True) -> Scene:
+    """The block on a horizontal SLIDE_FLOOR whose centre moves by `shift` in x every step (step k
+    runs against the centre at k shift). With friction the block is carried along; without it stays."""
+    sc = block_on_incline(0.0, friction, cells=cells, cell=cell, E=E, nu=nu, iters=iters, aa_m=aa_m, accel=accel,
+                          n_steps=n_steps, dt=dt, record=record)
+    sc.name = "block_on_moving_floor"
+    sc.obstacles = [(OBS_SLIDE_FLOOR, (0.0, 0.0, 0.0, 0.0, 1.0, 0.0))]
+    sc.obstacle_motion = [[(k * shift, 0.0, 0.0, 0.0, 1.0, 0.0)] for k in range(1, n_steps + 1)]
+    return sc
+
+
+def block_on_turntable(friction=None, *, dtheta=0.01, cells=(4, 2, 4), cell=0.25, E=1e7, nu=0.3, iters=40, aa_m=5,
+                       accel=1, n_steps=40, dt=1.0 / 60.0, record=True) -> Scene:
+    """The block on a slab mesh (a box, its top face at y = 0) that turns about the y axis by
+    `dtheta` per step through its pose (step k runs against the slab turned by k dtheta). With
+    friction the block turns with the slab. Obstacle row 0 is the mesh."""
+    sc = block_on_incline(0.0, None, cells=cells, cell=cell, E=E, nu=nu, iters=iters, aa_m=aa_m, accel=accel,
+                          n_steps=n_steps, dt=dt, record=record)
+    sc.name = "block_on_turntable"
+    sc.obstacles = []
+    ext = 2.0 * cell * max(cells[0], cells[2])
+    V = np.array([[x, y, z] for x in (-ext, ext) for y in (-0.5 * ext, 0.0) for z in (-ext, ext)])
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]   # outward
+    F = np.array([tri for a, b, c, d in quads for tri in ((a, b, c), (a, c, d))], np.int32)
+    sc.mesh_obstacles = [(V, F)]
+    poses = np.zeros((n_steps, 1, 12))
+    for k in range(n_steps):
+        poses[k, 0, :9] = rotation_y((k + 1) * dtheta).reshape(9)
+    sc.mesh_obstacle_poses = poses
+    sc.obstacle_friction = None if friction is None else [friction]
     return sc

@@ -167,8 +167,9 @@ int aa_elastic_add_mesh_obstacle(aa_elastic h, const double* verts3, int n_verts
  * A mesh that never had a pose set takes exactly the unposed arithmetic. May be called before or
  * after initialize and between steps; it writes the mesh's row of the device table on the solver's
  * stream and keeps the captured step graph. The pose holds for every ADMM iteration of every later
- * step until changed. The obstacle is kinematic: it has no velocity and exerts no friction; a node
- * it overruns is moved to its surface by the next step's prox. R is used as given (no
+ * step until changed. The obstacle is kinematic; it exerts friction, and carries the nodes on it
+ * along, only through aa_elastic_set_obstacle_friction (below). A node it overruns is moved to its
+ * surface by the next step's prox. R is used as given (no
  * re-orthonormalisation). AA_ERR_ARG, the message naming the cause: an unknown mesh_id, a
  * non-finite entry, max|R^T R - I| > 1e-12, det R <= 0 (a reflection would turn the surface
  * inside out). Partitioned solvers: every rank makes the same call, as for add_obstacle.
@@ -203,7 +204,8 @@ int aa_elastic_get_mesh_obstacle_pose(aa_elastic h, int mesh_id, double pose12[1
  * or after initialize and between steps; the work runs on the solver's stream and is finished when
  * the call returns; every device buffer and the mesh's table row keep their addresses, so the
  * captured step graph is kept. The vertices hold for every ADMM iteration of every later step until
- * changed. The obstacle stays kinematic: it has no velocity and exerts no friction. Validation
+ * changed. The obstacle stays kinematic; the friction pass (aa_elastic_set_obstacle_friction) takes
+ * no displacement from a change of shape. Validation
  * happens on the host before anything on the device is touched, and a refused call leaves the
  * obstacle exactly as it was. AA_ERR_ARG, the message naming the cause: an unknown mesh_id, a null
  * pointer, a non-finite coordinate (the vertex named), a zero-area triangle (named; the test of
@@ -222,8 +224,9 @@ int aa_elastic_get_mesh_obstacle_vertices(aa_elastic h, int mesh_id, double* ver
  * stream: no host copy, no wait. That work precedes the captured iteration graph, so binding and
  * unbinding keep the graph.
  * Coupling: the obstacle holds its start-of-step shape for every ADMM iteration of that step --
- * lagged, explicit coupling. It has no velocity and exerts no friction, and it is refitted once per
- * step, not more often. The BVH is not rebuilt when the shape drifts far from the added one: the
+ * lagged, explicit coupling. The friction pass (aa_elastic_set_obstacle_friction) treats its surface
+ * as standing still and applies no reaction to its nodes, and it is refitted once per step, not
+ * more often. The BVH is not rebuilt when the shape drifts far from the added one: the
  * cost growth stated above for the vertex setter applies alike.
  * Validity is decided on the device, because the host never sees the gathered shape. The causes
  * are the vertex setter's, tested in this order, the lowest-numbered one reported:
@@ -245,8 +248,8 @@ int aa_elastic_get_mesh_obstacle_vertices(aa_elastic h, int mesh_id, double* ver
  * count, a node index out of range, a mesh that has a pose, a solver partitioned over more than one
  * rank (a rank holds only its part of the nodes: partitioned binding is out of scope).
  * aa_elastic_set_mesh_obstacle_pose and aa_elastic_set_mesh_obstacle_vertices refuse a bound mesh.
- * Not provided: self-collision (see the exemption below), partitioned solvers, friction or obstacle
- * velocity, more than one refit per step, a BVH rebuild on drift, and the z-AA variant, which
+ * Not provided: self-collision (see the exemption below), partitioned solvers, friction against the
+ * surface's own motion, more than one refit per step, a BVH rebuild on drift, and the z-AA variant, which
  * refuses collision terms as before. */
 int aa_elastic_bind_mesh_obstacle(aa_elastic h, int mesh_id, const int* nodes, int n_verts);
 int aa_elastic_mesh_obstacle_status(aa_elastic h, int mesh_id, int* bound, int* refits, int* skipped, int* last_cause);
@@ -267,6 +270,57 @@ int aa_elastic_num_obstacles(aa_elastic h, int* n);
  * `type` must equal the row's stored type (a guard against a stale index). AA_ERR_ARG for a mesh
  * row, a type mismatch, an index out of range, null or non-finite parameters. */
 int aa_elastic_set_obstacle(aa_elastic h, int index, int type, const double* params);
+/* Coulomb friction of the collision terms against the obstacles, moving ones included. mu is the
+ * coefficient of obstacle row `index` of the shared insertion order, analytic and mesh alike
+ * (default 0). May be set before or after initialize and between steps; the captured step graph is
+ * kept, because friction is one pass per step after the ADMM iterations and before the new state is
+ * formed, outside that graph. The pass runs in a step iff some row has mu > 0 or recording is on; a
+ * solver that uses neither launches nothing new and computes bit for bit what it did.
+ * The model, per collision term on a node of mass m (term weight w, penalty p, time step dt), on
+ * the pair (u, x_new) the step writes back (with Anderson acceleration the un-accelerated pair of
+ * the last iteration); fp64, no FMA contraction, sums left to right:
+ *   1  q = (1/w) (w x_new + u), the point the last local step's prox saw. The prox is a hard
+ *      projection, so a converged x_new lies on the surface and the dual pushes q inside: contact is
+ *      decided on q.
+ *   2  The obstacle walk of the collision prox on q, every rule unchanged (insertion order, a later
+ *      analytic obstacle wins a tie, a mesh hit replaces unconditionally, exemptions, poses, the
+ *      root-box cull). Contact iff the final dx < 0; r = the row that supplied it, c = its point.
+ *   3  e = c - q, l = sqrt((e0^2 + e1^2) + e2^2), n = e / l; no contact if l == 0.
+ *   4  un = (u0 n0 + u1 n1) + u2 n2, k = (((p dt) dt) w) / m, j = k (-un) if un < 0, else 0: the
+ *      length dt^2 f_n / m for the term's normal force f_n on the node in the step's optimality
+ *      condition M (x - xbar) = -p dt^2 D^T u, D = w I.
+ *   5  g = the obstacle's displacement at c between its state during the previous step and now:
+ *      FLOOR (0, y_now - y_prev, 0); the other analytic shapes centre_now - centre_prev (changes of
+ *      normal or radius do not count); a mesh c - ((R_prev c_l) + t_prev) with c_l = c taken into
+ *      the obstacle frame of the pose now (no pose = identity) -- the position form, not omega x c,
+ *      so a node stuck to a turning obstacle does not drift along the tangent. g = 0 for a mesh
+ *      whose vertices changed since the previous step (aa_elastic_set_mesh_obstacle_vertices) or
+ *      that is bound to solver nodes. In the first step, and in the first step after a step in
+ *      which the pass did not run, previous = now.
+ *   6  rel = (x_new - x_old) - g, rn = (rel0 n0 + rel1 n1) + rel2 n2, rt = rel - rn n,
+ *      lt = sqrt((rt0^2 + rt1^2) + rt2^2); s = 0 if mu_r == 0, j == 0 or !(lt > 0), else
+ *      min(1, (mu_r j) / lt); x_new -= s rt, written only when s != 0.
+ * The velocity is then (x_new' - x_old) / dt as always. s = 1: the node does not move along the
+ * surface relative to the obstacle (static friction); s < 1: it loses mu j of slip (kinetic).
+ * A collision term on a pinned node is reported but never filtered.
+ * What it is not: the friction is lagged and explicit, applied once per step with the normal force
+ * of the solve just finished -- it is not part of the ADMM iteration; there is no rolling or
+ * anisotropic friction, no friction from a deforming or bound mesh's own surface motion, and no
+ * reaction on a bound obstacle's nodes.
+ * aa_elastic_record_contacts(on) keeps the pass running for its records even with every mu = 0.
+ * aa_elastic_get_contacts returns the last step's terms in contact, in collision-term order: *n
+ * their full count, at most cap entries in each given array (every array may be NULL) -- the node
+ * (caller's numbering), the obstacle row r, the point c, the normal n, the push j, the slip rt
+ * and the scale s. n = 0 when the pass did not run in the last step.
+ * AA_ERR_ARG, the message naming the cause: an index out of range, a negative or non-finite mu, a
+ * null mu or n output, and mu > 0 or recording on in a solver partitioned over more than one rank
+ * (a rank holds only its part of the terms), raised by the setter after initialize and by
+ * aa_elastic_initialize otherwise. */
+int aa_elastic_set_obstacle_friction(aa_elastic h, int index, double mu);
+int aa_elastic_get_obstacle_friction(aa_elastic h, int index, double* mu);
+int aa_elastic_record_contacts(aa_elastic h, int on);
+int aa_elastic_get_contacts(aa_elastic h, int cap, int* n, int* node, int* obstacle, double* point3, double* normal3,
+                            double* push, double* slip3, double* scale);
 /* Solver::set_collisions(inds, points) (admm_anderson_hard_zxu/src/Solver.cpp:318-344): one
  * Collision energy term (CollisionEnergyTerm.hpp:41-117: identity reduction, weight
  * sqrt(2 k(soft rubber)), prox = closest obstacle surface point when inside one) per listed node,
@@ -487,7 +541,13 @@ int aa_geom_set_comm(aa_geom h, aa_comm c);
  *     and vol6, the check's chunked sum; ms (optional, device = 1): the device time of gather +
  *     check + refit by device events, the median of 5 runs after a warm-up.
  *   aa_test_collision_prox_exempt: aa_test_collision_prox_posed with a node id per query (q_node)
- *     and per mesh a list of exempt nodes (mesh m: exempt_nodes[exempt_ptr[m]..exempt_ptr[m+1])). */
+ *     and per mesh a list of exempt nodes (mesh m: exempt_nodes[exempt_ptr[m]..exempt_ptr[m+1])).
+ *   aa_test_contact_friction: the friction pass's device function (aa_elastic_set_obstacle_friction)
+ *     on n queries. Obstacle rows now and previous (8 doubles each, same types) with mu per row; the
+ *     concatenated meshes with poses now and previous (12 doubles per mesh, a row of NaNs = no
+ *     pose) and mesh_still (optional; non-zero = g is 0 for that mesh); per query the exemption
+ *     node id, a pinned flag, x_old, x_new, u, w, m; p and dt. Outputs per query: x' (x_new's bits
+ *     where s = 0), the contact flag, the row, c, n, j, rt, s. */
 int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double* in, int n, double* out, int* iters);
 int aa_test_cod_solve(aa_ctx ctx, int k, const double* M, const double* b, double* theta);
 int aa_test_geom_project(aa_ctx ctx, int type, int k, const double* prm2, const double* in, int n, double* out);
@@ -515,6 +575,14 @@ int aa_test_collision_prox_exempt(aa_ctx ctx, const double* obs_rows, int n_obs,
                                   const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr, int n_meshes,
                                   const double* mesh_poses, const double* q3, const int* q_node, int n,
                                   const int* exempt_ptr, const int* exempt_nodes, double* out3);
+int aa_test_contact_friction(aa_ctx ctx, const double* obs_rows, const double* obs_rows_prev, const double* mu, int n_obs,
+                             const double* mesh_verts3, const int* mesh_vert_ptr, const int* mesh_tris3,
+                             const int* mesh_tri_ptr, int n_meshes, const double* mesh_poses,
+                             const double* mesh_poses_prev, const unsigned char* mesh_still, const int* q_node,
+                             const unsigned char* q_pinned, int n, const int* exempt_ptr, const int* exempt_nodes,
+                             const double* x_old3, const double* x_new3, const double* u3, const double* w,
+                             const double* m, double penalty, double dt, double* x_out3, int* hit, int* row,
+                             double* point3, double* normal3, double* push, double* slip3, double* scale);
 /* The global step's sparse triangular solve alone (DirectSolver, csrc/direct_solve.hpp), on a
  * caller-given SPD matrix: full-pattern symmetric CSR (ptr, col, val; sorted columns, every
  * diagonal stored) of order n in the caller's ordering, node coordinates xyz3.

@@ -16,6 +16,7 @@
 //   solver.set_obstacle_pose(mesh, R, t); solver.update_obstacle(floor);   // kinematic obstacles, between steps
 //   solver.set_obstacle_vertices(mesh, new_verts);                         // a mesh that changes shape
 //   solver.bind_obstacle(mesh, surface_nodes); solver.exempt_from_obstacle(mesh, body_nodes);   // body-to-body contact
+//   solver.set_obstacle_friction(floor, 0.4); solver.record_contacts(); solver.contacts();      // Coulomb friction
 //
 // Energy terms are descriptors of the built-in element kinds (batched SoA on the device);
 // user-defined EnergyTerm subclasses with arbitrary prox() are not supported (no host
@@ -343,6 +344,42 @@ public:
         const int row = row_of(obj.get());
         if (row < 0) throw std::runtime_error("update_obstacle: the obstacle was not added to this solver");
         check(aa_elastic_set_obstacle(h_, row, obj->type, obj->params));
+    }
+    // Coulomb friction against an obstacle (no reference counterpart: Collision::prox only projects;
+    // aa_admm.h, aa_elastic_set_obstacle_friction): the coefficient of the obstacle's row, moving
+    // obstacles included -- a block stays on an incline, a cloth turns with the drum under it. Lagged
+    // and explicit, one pass per step. record_contacts keeps the per-term records with every mu = 0.
+    void set_obstacle_friction(const std::shared_ptr<PassiveCollision>& obj, double mu) {
+        const int row = row_of(obj.get());
+        if (row < 0) throw std::runtime_error("set_obstacle_friction: the obstacle was not added to this solver");
+        check(aa_elastic_set_obstacle_friction(h_, row, mu));
+    }
+    double obstacle_friction(const std::shared_ptr<PassiveCollision>& obj) const {
+        const int row = row_of(obj.get());
+        if (row < 0) throw std::runtime_error("obstacle_friction: the obstacle was not added to this solver");
+        double mu = 0;
+        check(aa_elastic_get_obstacle_friction(h_, row, &mu));
+        return mu;
+    }
+    void record_contacts(bool on = true) { check(aa_elastic_record_contacts(h_, on ? 1 : 0)); }
+    // the last step's collision terms in contact, in term order
+    struct Contact {
+        int node, obstacle;         // the caller's node, the obstacle's row in the insertion order
+        Vec3 point, normal, slip;   // c, n, and the tangential slip rt relative to the obstacle
+        double push, scale;         // j = dt^2 f_n / m, and the share s of the slip taken away
+    };
+    std::vector<Contact> contacts() const {
+        int n = 0;
+        check(aa_elastic_get_contacts(h_, 0, &n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        std::vector<int> node(n), obs(n);
+        std::vector<double> pt(3 * (size_t)n), nr(3 * (size_t)n), sl(3 * (size_t)n), push(n), sc(n);
+        if (n) check(aa_elastic_get_contacts(h_, n, &n, node.data(), obs.data(), pt.data(), nr.data(), push.data(), sl.data(), sc.data()));
+        std::vector<Contact> out(n);
+        for (int k = 0; k < n; ++k) {
+            out[k].node = node[k]; out[k].obstacle = obs[k]; out[k].push = push[k]; out[k].scale = sc[k];
+            for (int i = 0; i < 3; ++i) { out[k].point[i] = pt[3 * k + i]; out[k].normal[i] = nr[3 * k + i]; out[k].slip[i] = sl[3 * k + i]; }
+        }
+        return out;
     }
     // Solver::set_collisions (Solver.cpp:318-344): the points are not used by the prox
     // Before the first initialize() the device solver has no nodes yet (see below): the list is
