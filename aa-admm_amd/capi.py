@@ -28,7 +28,8 @@ EXPORTS = [
     "aa_elastic_get_mesh_obstacle_pose", "aa_elastic_set_mesh_obstacle_vertices", "aa_elastic_get_mesh_obstacle_vertices",
     "aa_elastic_bind_mesh_obstacle", "aa_elastic_mesh_obstacle_status", "aa_elastic_set_mesh_obstacle_exempt",
     "aa_elastic_num_obstacles", "aa_elastic_set_obstacle", "aa_elastic_set_obstacle_friction", "aa_elastic_get_obstacle_friction",
-    "aa_elastic_record_contacts", "aa_elastic_get_contacts", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
+    "aa_elastic_record_contacts", "aa_elastic_get_contacts", "aa_elastic_set_mesh_obstacle_carry", "aa_elastic_get_mesh_obstacle_carry",
+    "aa_elastic_get_contact_features", "aa_elastic_set_collisions", "aa_elastic_add_wind", "aa_elastic_set_wind",
     "aa_elastic_num_nodes", "aa_elastic_get_x", "aa_elastic_get_v", "aa_elastic_set_v", "aa_elastic_get_history",
     "aa_elastic_get_times", "aa_elastic_set_iterations", "aa_elastic_set_x",
     "aa_elastic_runtime", "aa_elastic_bench_iterations", "aa_elastic_kernel_stats", "aa_elastic_local_stats",
@@ -40,7 +41,7 @@ EXPORTS = [
     "aa_geom_runtime_info", "aa_geom_closest_points", "aa_geom_bench_iterations", "aa_geom_kernel_stats",
     "aa_test_prox", "aa_test_cod_solve", "aa_test_geom_project", "aa_test_mesh_sdf", "aa_test_collision_prox",
     "aa_test_mesh_sdf_posed", "aa_test_collision_prox_posed", "aa_test_mesh_refit_tables", "aa_test_mesh_sdf_deformed", "aa_test_direct_solve",
-    "aa_test_bound_refit", "aa_test_collision_prox_exempt", "aa_test_contact_friction",
+    "aa_test_bound_refit", "aa_test_collision_prox_exempt", "aa_test_contact_friction", "aa_test_contact_friction_carry",
 ]
 
 # Geometry constraint types (Geometry/Constraint.h) and SPD solver types (SolverCommon.h)
@@ -471,6 +472,30 @@ class Solver:
                                                _dp(sl), _dp(sc)))
         return dict(node=node[:k], obstacle=obs[:k], point=pt[:k], normal=nr[:k], push=push[:k], slip=sl[:k], scale=sc[:k])
 
+    def set_mesh_obstacle_carry(self, mesh_id, on=True):
+        """Carry, per mesh, default off: the friction pass takes this mesh's displacement at a contact
+        from its vertices' own motion since the previous step's pass, so a mesh moved through
+        set_mesh_obstacle_vertices or bound to solver nodes drags the nodes on it as a posed one does.
+        Before or after initialize, between steps; the step graph is kept."""
+        _chk(lib().aa_elastic_set_mesh_obstacle_carry(self.h, C.c_int(mesh_id), C.c_int(1 if on else 0)))
+
+    def mesh_obstacle_carry(self, mesh_id):
+        on = C.c_int()
+        _chk(lib().aa_elastic_get_mesh_obstacle_carry(self.h, C.c_int(mesh_id), C.byref(on)))
+        return bool(on.value)
+
+    def contact_features(self):
+        """The last step's contacts in contacts()'s order: dict(tri (the caller's triangle index, -1
+        for an analytic row), bary (k, 3) the barycentric weights of the contact point on it). Empty
+        when that step's pass was not the carry form."""
+        n = C.c_int()
+        _chk(lib().aa_elastic_get_contact_features(self.h, C.c_int(0), C.byref(n), None, None))
+        k = n.value
+        tri, b = np.zeros(max(k, 1), np.int32), np.zeros((max(k, 1), 3))
+        if k:
+            _chk(lib().aa_elastic_get_contact_features(self.h, C.c_int(k), C.byref(n), _ip(tri), _dp(b)))
+        return dict(tri=tri[:k], bary=b[:k])
+
     def set_collisions(self, inds):
         i = np.ascontiguousarray(inds, np.int32).reshape(-1)
         _chk(lib().aa_elastic_set_collisions(self.h, _ip(i), C.c_int(len(i))))
@@ -525,6 +550,11 @@ class Solver:
         out = np.zeros(3 * self.num_nodes())
         _chk(lib().aa_elastic_get_v(self.h, _dp(out)))
         return out.reshape(-1, 3)
+
+    def set_v(self, v):
+        """Solver::m_v assignment between steps (velocities, n x 3)."""
+        v = np.ascontiguousarray(v, np.float64).reshape(-1)
+        _chk(lib().aa_elastic_set_v(self.h, _dp(v)))
 
     def set_state(self, x, v):
         """Solver::m_x / m_v assignment between steps (positions and velocities, n x 3)."""
@@ -642,6 +672,9 @@ def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
             s.set_obstacle_friction(row, mu)
     if getattr(scene, "record_contacts", False):
         s.record_contacts(True)
+    for m, on in enumerate(getattr(scene, "mesh_obstacle_carry", None) or []):
+        if on:
+            s.set_mesh_obstacle_carry(m, True)
     return s
 
 
@@ -655,6 +688,8 @@ def run_scene(ctx: Context, scene, n_steps=None, comm=None):
     """Runs the scene like the reference driver; returns per-step dicts (prim, comb, reject, x, v)."""
     s = solver_from_scene(ctx, scene, comm)
     s.initialize(settings_from_scene(scene))
+    if getattr(scene, "initial_velocity", None) is not None:
+        s.set_v(scene.initial_velocity)
     out = []
     n_steps = scene.n_steps if n_steps is None else n_steps
     for k in range(1, n_steps + 1):
@@ -1030,7 +1065,7 @@ def hook_collision_prox_exempt(ctx: Context, obstacles, meshes, Q, q_nodes, exem
 
 
 def hook_contact_friction(ctx: Context, obstacles, obstacles_prev, mu, meshes, x_old, x_new, u, w, m, penalty, dt,
-                          q_nodes=None, pinned=None, exempt=None, poses=None, poses_prev=None, mesh_still=None):
+                          q_nodes=None, pinned=None, exempt=None, poses=None, poses_prev=None, mesh_still=None, _carry=None):
     """The friction pass's device function (aa_test_contact_friction) on n queries. obstacles /
     obstacles_prev: (type, params) rows now and during the previous step (a mesh as (AA_OBS_MESH,
     [k]) naming meshes[k] = (V, F)), mu one coefficient per row; poses / poses_prev: per mesh (R, t),
@@ -1083,13 +1118,38 @@ def hook_contact_friction(ctx: Context, obstacles, obstacles_prev, mu, meshes, x
     k1 = max(n, 1)
     x, hit, row = np.zeros((k1, 3)), np.zeros(k1, np.int32), np.zeros(k1, np.int32)
     pt, nr, sl, push, sc = np.zeros((k1, 3)), np.zeros((k1, 3)), np.zeros((k1, 3)), np.zeros(k1), np.zeros(k1)
-    _chk(lib().aa_test_contact_friction(
-        ctx.h, _dp(rows), _dp(rows_prev), _dp(mus), C.c_int(len(obstacles)), _dp(vv), _ip(vptr), _ip(ff), _ip(fptr),
-        C.c_int(len(meshes)), _dp(pp), _dp(pq), _ub(still), _ip(qn), _ub(pin), C.c_int(n), _ip(eptr), _ip(enodes), _dp(xo),
-        _dp(xn), _dp(uu), _dp(ww), _dp(mm), C.c_double(penalty), C.c_double(dt), _dp(x), _ip(hit), _ip(row), _dp(pt), _dp(nr),
-        _dp(push), _dp(sl), _dp(sc)))
-    return dict(x=x[:n], hit=hit[:n].astype(bool), row=row[:n], point=pt[:n], normal=nr[:n], push=push[:n], slip=sl[:n],
-                scale=sc[:n])
+    head = (ctx.h, _dp(rows), _dp(rows_prev), _dp(mus), C.c_int(len(obstacles)), _dp(vv), _ip(vptr), _ip(ff), _ip(fptr),
+            C.c_int(len(meshes)), _dp(pp), _dp(pq), _ub(still), _ip(qn), _ub(pin), C.c_int(n), _ip(eptr), _ip(enodes), _dp(xo),
+            _dp(xn), _dp(uu), _dp(ww), _dp(mm), C.c_double(penalty), C.c_double(dt))
+    outs = (_dp(x), _ip(hit), _ip(row), _dp(pt), _dp(nr), _dp(push), _dp(sl), _dp(sc))
+    result = lambda: dict(x=x[:n], hit=hit[:n].astype(bool), row=row[:n], point=pt[:n], normal=nr[:n], push=push[:n],
+                          slip=sl[:n], scale=sc[:n])
+    if _carry is None:
+        _chk(lib().aa_test_contact_friction(*head, *outs))
+        return result()
+    verts_prev, flags = _carry
+    if len(verts_prev) != len(meshes) or len(flags) != len(meshes):
+        raise ValueError("hook_contact_friction_carry: previous vertices and a carry flag per mesh")
+    ps = [np.ascontiguousarray(vs[k] if P is None else P, np.float64).reshape(-1, 3) for k, P in enumerate(verts_prev)]
+    if any(a.shape != b.shape for a, b in zip(ps, vs)):
+        raise ValueError("hook_contact_friction_carry: the previous vertices differ in count from the mesh's")
+    vp = np.ascontiguousarray(np.concatenate(ps) if ps else np.zeros((1, 3)))
+    cf = np.ascontiguousarray(np.concatenate([np.asarray(flags, np.float64).reshape(-1), np.zeros(1)]), np.uint8)
+    tri, b = np.zeros(k1, np.int32), np.zeros((k1, 3))
+    _chk(lib().aa_test_contact_friction_carry(*head, _dp(vp), _ub(cf), *outs, _ip(tri), _dp(b)))
+    out = result()
+    out.update(tri=tri[:n], bary=b[:n])
+    return out
+
+
+def hook_contact_friction_carry(ctx: Context, obstacles, obstacles_prev, mu, meshes, x_old, x_new, u, w, m, penalty, dt,
+                                verts_prev, carry, **kw):
+    """The carry form of the pass's device function (aa_test_contact_friction_carry):
+    hook_contact_friction's arguments plus, per mesh, the previous vertices (n, 3) (None = the mesh's
+    own) and the carry flag. Also returns tri (the caller's triangle index of a mesh-row contact, -1
+    otherwise) and bary (n, 3)."""
+    return hook_contact_friction(ctx, obstacles, obstacles_prev, mu, meshes, x_old, x_new, u, w, m, penalty, dt,
+                                 _carry=(verts_prev, carry), **kw)
 
 
 def hook_mesh_sdf_deformed(ctx: Context, V, F, V_new, Q, pose=None, timings=False):

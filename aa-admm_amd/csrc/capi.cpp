@@ -296,6 +296,32 @@ int aa_elastic_get_contacts(aa_elastic h, int cap, int* n, int* node, int* obsta
     });
 }
 
+int aa_elastic_set_mesh_obstacle_carry(aa_elastic h, int mesh_id, int on) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
+        h->s->set_mesh_obstacle_carry(mesh_id, on != 0);
+    });
+}
+
+int aa_elastic_get_mesh_obstacle_carry(aa_elastic h, int mesh_id, int* on) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        NEED(on, "aa_elastic_get_mesh_obstacle_carry: null on");
+        *on = h->s->mesh_obstacle_carry(mesh_id) ? 1 : 0;
+    });
+}
+
+int aa_elastic_get_contact_features(aa_elastic h, int cap, int* n, int* tri, double* bary3) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        NEED(n, "aa_elastic_get_contact_features: null n");
+        NEED(cap >= 0, "aa_elastic_get_contact_features: negative cap");
+        AA_HIP(hipSetDevice(h->ctx->c.device));
+        *n = h->s->contact_features(cap, tri, bary3);
+    });
+}
+
 int aa_elastic_set_collisions(aa_elastic h, const int* inds, int n) {
     return guarded([&] { NEED(h, "null handle"); h->s->set_collisions(inds, n); });
 }
@@ -933,16 +959,20 @@ extern "C" int aa_test_collision_prox_exempt(aa_ctx ctx, const double* obs_rows,
     });
 }
 
-extern "C" int aa_test_contact_friction(aa_ctx ctx, const double* obs_rows, const double* obs_rows_prev, const double* mu,
-                                       int n_obs, const double* mesh_verts3, const int* mesh_vert_ptr, const int* mesh_tris3,
-                                       const int* mesh_tri_ptr, int n_meshes, const double* mesh_poses,
-                                       const double* mesh_poses_prev, const unsigned char* mesh_still, const int* q_node,
-                                       const unsigned char* q_pinned, int n, const int* exempt_ptr, const int* exempt_nodes,
-                                       const double* x_old3, const double* x_new3, const double* u3, const double* w,
-                                       const double* m, double penalty, double dt, double* x_out3, int* hit, int* row,
-                                       double* point3, double* normal3, double* push, double* slip3, double* scale) {
+// aa_test_contact_friction and its carry form (carry_form: mesh_verts_prev3, mesh_carry, tri and
+// bary3 are read / written and the carry kernel is launched; otherwise the plain one, as ever)
+static int test_contact_friction(const char* who, bool carry_form, aa_ctx ctx, const double* obs_rows,
+                                 const double* obs_rows_prev, const double* mu, int n_obs, const double* mesh_verts3,
+                                 const int* mesh_vert_ptr, const int* mesh_tris3, const int* mesh_tri_ptr, int n_meshes,
+                                 const double* mesh_poses, const double* mesh_poses_prev, const unsigned char* mesh_still,
+                                 const int* q_node, const unsigned char* q_pinned, int n, const int* exempt_ptr,
+                                 const int* exempt_nodes, const double* x_old3, const double* x_new3, const double* u3,
+                                 const double* w, const double* m, double penalty, double dt, double* x_out3, int* hit,
+                                 int* row, double* point3, double* normal3, double* push, double* slip3, double* scale,
+                                 const double* mesh_verts_prev3, const unsigned char* mesh_carry, int* tri, double* bary3) {
     return with_device_arrays(ctx, [&](hipStream_t s) {
-        const char* who = "aa_test_contact_friction: ";
+        NEED(!carry_form || ((n_meshes == 0 || (mesh_verts_prev3 && mesh_carry)) && tri && bary3),
+             std::string(who) + "null carry arguments");
         NEED(n >= 0 && n_obs >= 0 && n_obs <= aa::kMaxObstacles && (n_obs == 0 || (obs_rows && obs_rows_prev && mu)),
              std::string(who) + "bad obstacle arguments");
         NEED(n_meshes >= 0 && n_meshes <= aa::kMaxMeshObstacles, std::string(who) + "too many mesh obstacles");
@@ -967,6 +997,9 @@ extern "C" int aa_test_contact_friction(aa_ctx ctx, const double* obs_rows, cons
         std::vector<std::unique_ptr<aa::MeshObsBuffers>> bufs;
         std::vector<aa::MeshObsDev> table((size_t)aa::kMaxMeshObstacles), prev((size_t)aa::kMaxMeshObstacles);
         std::vector<unsigned char> still((size_t)aa::kMaxMeshObstacles, 0);
+        std::vector<aa::MeshCarryDev> ctab((size_t)aa::kMaxMeshObstacles, aa::MeshCarryDev{nullptr, nullptr});
+        std::vector<std::unique_ptr<aa::DevBuf<double>>> vprev;
+        std::vector<std::unique_ptr<aa::DevBuf<int>>> lvid;
         auto pose_of = [&](const double* poses, int k) -> const double* {
             const double* pose = poses ? poses + 12 * (size_t)k : nullptr;
             if (pose && std::all_of(pose, pose + 12, [](double v) { return std::isnan(v); })) pose = nullptr;
@@ -990,6 +1023,16 @@ extern "C" int aa_test_contact_friction(aa_ctx ctx, const double* obs_rows, cons
                 ebufs.back()->upload(bytes, s);
                 AA_HIP(hipStreamSynchronize(s));
                 table[k].exempt = ebufs.back()->p;
+            }
+            if (carry_form && mesh_carry[k]) {   // the previous vertices and the leaf triangles' vertex ids
+                const int nv = mesh_vert_ptr[k + 1] - mesh_vert_ptr[k], nf = mesh_tri_ptr[k + 1] - mesh_tri_ptr[k];
+                const aa::MeshRefitTables RT = aa::make_refit_tables(M, nv, mesh_tris3 + 3 * (size_t)mesh_tri_ptr[k], nf);
+                vprev.push_back(std::make_unique<aa::DevBuf<double>>());
+                lvid.push_back(std::make_unique<aa::DevBuf<int>>());
+                vprev.back()->upload(mesh_verts_prev3 + 3 * (size_t)mesh_vert_ptr[k], 3 * (size_t)nv, s);
+                lvid.back()->upload(RT.leaf_vid, s);
+                AA_HIP(hipStreamSynchronize(s));   // RT is a temporary
+                ctab[k] = aa::MeshCarryDev{vprev.back()->p, lvid.back()->p};
             }
         }
         std::vector<double> h(1 + (size_t)aa::kObsStride * aa::kMaxObstacles, 0.0), hp(h.size(), 0.0), hmu((size_t)aa::kMaxObstacles, 0.0);
@@ -1022,8 +1065,21 @@ extern "C" int aa_test_contact_friction(aa_ctx ctx, const double* obs_rows, cons
             dw.upload(w, (size_t)n, s); dm.upload(m, (size_t)n, s);
             const aa::FrictionTables T{dobsp.p, dprev.p, dmu.p, dstill.p};
             const aa::ContactRecDev rec{dhit.p, drow.p, dc.p, dn.p, dj.p, drt.p, ds.p};
-            aa::launch_test_contact_friction(dobs.p, n_meshes > 0 ? dtab.p : nullptr, T, dnode.p, dpin.p, dxo.p, dxn.p, du.p,
-                                             dw.p, dm.p, penalty, dt, n, rec, s);
+            aa::DevBuf<aa::MeshCarryDev> dcarry;
+            aa::DevBuf<int> dtri;
+            aa::DevBuf<double> db;
+            if (carry_form) {
+                dcarry.upload(ctab, s);
+                dtri.alloc(nn); db.alloc(3 * nn);
+                aa::launch_test_contact_friction_carry(dobs.p, n_meshes > 0 ? dtab.p : nullptr, T, dnode.p, dpin.p, dxo.p, dxn.p,
+                                                       du.p, dw.p, dm.p, penalty, dt, n, rec, dcarry.p,
+                                                       aa::ContactFeatDev{dtri.p, db.p}, s);
+                AA_HIP(hipMemcpyAsync(tri, dtri.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+                AA_HIP(hipMemcpyAsync(bary3, db.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+            } else {
+                aa::launch_test_contact_friction(dobs.p, n_meshes > 0 ? dtab.p : nullptr, T, dnode.p, dpin.p, dxo.p, dxn.p, du.p,
+                                                 dw.p, dm.p, penalty, dt, n, rec, s);
+            }
             AA_HIP(hipMemcpyAsync(x_out3, dxn.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
             AA_HIP(hipMemcpyAsync(hit, dhit.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
             AA_HIP(hipMemcpyAsync(row, drow.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
@@ -1032,9 +1088,41 @@ extern "C" int aa_test_contact_friction(aa_ctx ctx, const double* obs_rows, cons
             AA_HIP(hipMemcpyAsync(push, dj.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
             AA_HIP(hipMemcpyAsync(slip3, drt.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
             AA_HIP(hipMemcpyAsync(scale, ds.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+            AA_HIP(hipStreamSynchronize(s));   // the carry form's buffers live in this block
         }
         AA_HIP(hipStreamSynchronize(s));
     });
+}
+
+extern "C" int aa_test_contact_friction(aa_ctx ctx, const double* obs_rows, const double* obs_rows_prev, const double* mu,
+                                       int n_obs, const double* mesh_verts3, const int* mesh_vert_ptr, const int* mesh_tris3,
+                                       const int* mesh_tri_ptr, int n_meshes, const double* mesh_poses,
+                                       const double* mesh_poses_prev, const unsigned char* mesh_still, const int* q_node,
+                                       const unsigned char* q_pinned, int n, const int* exempt_ptr, const int* exempt_nodes,
+                                       const double* x_old3, const double* x_new3, const double* u3, const double* w,
+                                       const double* m, double penalty, double dt, double* x_out3, int* hit, int* row,
+                                       double* point3, double* normal3, double* push, double* slip3, double* scale) {
+    return test_contact_friction("aa_test_contact_friction: ", false, ctx, obs_rows, obs_rows_prev, mu, n_obs, mesh_verts3,
+                                 mesh_vert_ptr, mesh_tris3, mesh_tri_ptr, n_meshes, mesh_poses, mesh_poses_prev, mesh_still, q_node,
+                                 q_pinned, n, exempt_ptr, exempt_nodes, x_old3, x_new3, u3, w, m, penalty, dt, x_out3, hit, row,
+                                 point3, normal3, push, slip3, scale, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int aa_test_contact_friction_carry(aa_ctx ctx, const double* obs_rows, const double* obs_rows_prev, const double* mu,
+                                             int n_obs, const double* mesh_verts3, const int* mesh_vert_ptr,
+                                             const int* mesh_tris3, const int* mesh_tri_ptr, int n_meshes,
+                                             const double* mesh_poses, const double* mesh_poses_prev,
+                                             const unsigned char* mesh_still, const int* q_node, const unsigned char* q_pinned,
+                                             int n, const int* exempt_ptr, const int* exempt_nodes, const double* x_old3,
+                                             const double* x_new3, const double* u3, const double* w, const double* m,
+                                             double penalty, double dt, const double* mesh_verts_prev3,
+                                             const unsigned char* mesh_carry, double* x_out3, int* hit, int* row, double* point3,
+                                             double* normal3, double* push, double* slip3, double* scale, int* tri,
+                                             double* bary3) {
+    return test_contact_friction("aa_test_contact_friction_carry: ", true, ctx, obs_rows, obs_rows_prev, mu, n_obs, mesh_verts3,
+                                 mesh_vert_ptr, mesh_tris3, mesh_tri_ptr, n_meshes, mesh_poses, mesh_poses_prev, mesh_still, q_node,
+                                 q_pinned, n, exempt_ptr, exempt_nodes, x_old3, x_new3, u3, w, m, penalty, dt, x_out3, hit, row,
+                                 point3, normal3, push, slip3, scale, mesh_verts_prev3, mesh_carry, tri, bary3);
 }
 
 extern "C" int aa_test_direct_solve(aa_ctx ctx, int n, const double* xyz3, const int* ptr, const int* col,

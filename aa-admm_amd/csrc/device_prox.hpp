@@ -378,12 +378,16 @@ __device__ inline void collision_prox(const double* q, const double* obs, double
 // final (dx, point): contact iff the final dx < 0, then row = that obstacle's index in the shared
 // insertion order and c its point in the world frame. Only the friction pass calls it
 // (contact_friction.hip); collision_prox and the kernels built from it are untouched.
+// collision_contact_walk also hands on the leaf triangle of the mesh hit that supplied the point
+// (-1 for an analytic row): what the carry form of the pass interpolates the surface's own motion
+// on. collision_contact, the plain pass's, drops it.
 template <class... M>
-__device__ inline bool collision_contact(const double* q, const double* obs, int& row, double* c, M... meshes) {
+__device__ inline bool collision_contact_walk(const double* q, const double* obs, int& row, double* c, int& tri_at,
+                                              M... meshes) {
 #pragma clang fp contract(off)
     double best = 1.79769313486231570815e+308;
     double pt[3] = {0.0, 0.0, 0.0};
-    int at = -1;
+    int at = -1, tat = -1;
     const int n = obs ? (int)obs[0] : 0;
     auto sq3 = [](double a, double b, double c) { return (a * a + b * b) + c * c; };
     for (int k = 0; k < n; ++k) {
@@ -428,6 +432,7 @@ __device__ inline bool collision_contact(const double* q, const double* obs, int
                 best = dx;
                 pt[0] = cm[0]; pt[1] = cm[1]; pt[2] = cm[2];
                 at = k;
+                tat = tri;
             }
             continue;
         } else {
@@ -442,10 +447,17 @@ __device__ inline bool collision_contact(const double* q, const double* obs, int
         best = dx;
         pt[0] = p0; pt[1] = p1; pt[2] = p2;
         at = k;
+        tat = -1;
     }
     row = at;
+    tri_at = tat;
     c[0] = pt[0]; c[1] = pt[1]; c[2] = pt[2];
     return best < 0;
+}
+template <class... M>
+__device__ inline bool collision_contact(const double* q, const double* obs, int& row, double* c, M... meshes) {
+    int tri;
+    return collision_contact_walk(q, obs, row, c, tri, meshes...);
 }
 
 // Coulomb friction of one collision term, applied once per step between the ADMM loop and the
@@ -459,16 +471,70 @@ struct FrictionRec {
     int hit, row;
     double c[3], n[3], j, rt[3], s;
 };
+// Carry form: the trailing pack is (the carry table, the contact's features to fill). A mesh whose
+// row of the table is set carries: its displacement at c is interpolated from its vertices' own
+// motion on the contact triangle (mesh_carry_displacement) and it is never still; every other row
+// follows the plain rule. The features (tri, b) are written for every mesh-row contact. Without the
+// pack the code is the plain pass's.
+struct FrictionFeat {
+    int tri;        // the caller's triangle index (MeshObsDev::orig); -1 for an analytic row
+    double b[3];    // barycentric weights of c_l on its corners A, B, C
+};
+// b of c_l on leaf triangle v9 = (A, B, C): Cramer's rule on the edge Gram matrix, (1, 0, 0) for a
+// triangle with !(den > 0)
+__device__ inline void tri_barycentric(const double* v9, const double* cl, double* b) {
+#pragma clang fp contract(off)
+    double e1[3], e2[3], d[3];
+    for (int i = 0; i < 3; ++i) { e1[i] = v9[3 + i] - v9[i]; e2[i] = v9[6 + i] - v9[i]; d[i] = cl[i] - v9[i]; }
+    const double d11 = (e1[0] * e1[0] + e1[1] * e1[1]) + e1[2] * e1[2];
+    const double d12 = (e1[0] * e2[0] + e1[1] * e2[1]) + e1[2] * e2[2];
+    const double d22 = (e2[0] * e2[0] + e2[1] * e2[1]) + e2[2] * e2[2];
+    const double p1 = (d[0] * e1[0] + d[1] * e1[1]) + d[2] * e1[2];
+    const double p2 = (d[0] * e2[0] + d[1] * e2[1]) + d[2] * e2[2];
+    const double den = d11 * d22 - d12 * d12;
+    if (!(den > 0.0)) { b[0] = 1.0; b[1] = 0.0; b[2] = 0.0; return; }
+    b[1] = (d22 * p1 - d12 * p2) / den;
+    b[2] = (d11 * p2 - d12 * p1) / den;
+    b[0] = (1.0 - b[1]) - b[2];
+}
+// g of a carrying mesh at c (c_l in the obstacle frame now): the corners' displacements since the
+// previous step's pass interpolated with b, taken off c_l, and the result carried by the previous
+// pose. With unchanged vertices every corner difference is an exact zero and g is the rigid one.
+__device__ inline void mesh_carry_displacement(const MeshObsDev& prev, const MeshCarryDev& cy, int tri, const double* v9,
+                                               const double* b, const double* c, const double* cl, double* g) {
+#pragma clang fp contract(off)
+    const int* vid = cy.leaf_vid + 3 * (size_t)tri;
+    const double *A = cy.vprev + 3 * (size_t)vid[0], *B = cy.vprev + 3 * (size_t)vid[1], *C = cy.vprev + 3 * (size_t)vid[2];
+    double pl[3], cp[3];
+    for (int i = 0; i < 3; ++i) {
+        const double gl = (b[0] * (v9[i] - A[i]) + b[1] * (v9[3 + i] - B[i])) + b[2] * (v9[6 + i] - C[i]);
+        pl[i] = cl[i] - gl;
+    }
+    mesh_to_world(prev, pl, cp);
+    for (int i = 0; i < 3; ++i) g[i] = c[i] - cp[i];
+}
+__device__ __forceinline__ const MeshCarryDev* carry_table_of(const MeshCarryDev* t, FrictionFeat*) { return t; }
+__device__ __forceinline__ FrictionFeat* carry_feat_of(const MeshCarryDev*, FrictionFeat* f) { return f; }
+
+template <class... K>
 __device__ inline void contact_friction(const double* xo, double* xn, const double* u, double w, double m, double p,
                                         double dt, const double* obs, const MeshObsDev* meshes, int node,
-                                        const FrictionTables& T, bool filter, FrictionRec& r) {
+                                        const FrictionTables& T, bool filter, FrictionRec& r, K... carry) {
 #pragma clang fp contract(off)
     r.hit = 0; r.row = -1; r.j = 0.0; r.s = 0.0;
     for (int i = 0; i < 3; ++i) { r.c[i] = 0.0; r.n[i] = 0.0; r.rt[i] = 0.0; }
     double q[3], c[3];
     collision_candidate(xn, u, w, q);
     int row;
-    const bool in = meshes ? collision_contact(q, obs, row, c, meshes, node) : collision_contact(q, obs, row, c);
+    int tri = -1;
+    bool in;
+    if constexpr (sizeof...(K) != 0) {
+        FrictionFeat* f = carry_feat_of(carry...);
+        f->tri = -1; f->b[0] = 0.0; f->b[1] = 0.0; f->b[2] = 0.0;
+        in = meshes ? collision_contact_walk(q, obs, row, c, tri, meshes, node) : collision_contact_walk(q, obs, row, c, tri);
+    } else {
+        in = meshes ? collision_contact(q, obs, row, c, meshes, node) : collision_contact(q, obs, row, c);
+    }
     if (!in) return;
     const double e0 = c[0] - q[0], e1 = c[1] - q[1], e2 = c[2] - q[2];
     const double l = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
@@ -484,7 +550,21 @@ __device__ inline void contact_friction(const double* xo, double* xn, const doub
     const int nprev = (int)T.obs_prev[0];
     if (type == OBS_MESH) {
         const int mr = (int)o[1];
-        if (!T.mesh_still[mr]) {
+        if constexpr (sizeof...(K) != 0) {
+            const MeshCarryDev cy = carry_table_of(carry...)[mr];
+            FrictionFeat* f = carry_feat_of(carry...);
+            const double* v9 = meshes[mr].surf.tris[tri].v;
+            double cl[3], cp[3];
+            mesh_to_local(meshes[mr], c, cl);
+            tri_barycentric(v9, cl, f->b);
+            f->tri = meshes[mr].orig[tri];
+            if (cy.vprev) {
+                mesh_carry_displacement(T.mesh_prev[mr], cy, tri, v9, f->b, c, cl, g);
+            } else if (!T.mesh_still[mr]) {
+                mesh_to_world(T.mesh_prev[mr], cl, cp);
+                for (int i = 0; i < 3; ++i) g[i] = c[i] - cp[i];
+            }
+        } else if (!T.mesh_still[mr]) {
             double cl[3], cp[3];
             mesh_to_local(meshes[mr], c, cl);
             mesh_to_world(T.mesh_prev[mr], cl, cp);

@@ -25,6 +25,7 @@ namespace aa {
 
 ElasticSolver::~ElasticSolver() {
     if (fr_ev0_) { (void)hipEventDestroy(fr_ev0_); (void)hipEventDestroy(fr_ev1_); }
+    if (fr_ev2_) (void)hipEventDestroy(fr_ev2_);
     drop_graph();
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_join_) (void)hipEventDestroy(ev_join_);
@@ -1379,12 +1380,34 @@ void ElasticSolver::record_contacts(bool on) {
     fr_record_ = on;
 }
 
+// Carry. The device copy of the vertices in force (rf.verts) is what the carry form's previous
+// vertices are snapshot from; a mesh that was never refitted has none yet, so switching on makes
+// it current (a bound mesh's is the device's own once the binding is uploaded).
+void ElasticSolver::set_mesh_obstacle_carry(int mesh_id, bool on) {
+    const std::string who = "set_mesh_obstacle_carry: ";
+    MeshObsBuffers& mo = mesh_at(mesh_id, who);
+    if (on && initialized_ && comm_ && comm_->size() > 1)
+        throw Error(ERR_ARG, who + "the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (a rank holds only its part of the collision terms; friction needs one rank)");
+    if (on && !mo.carry) {
+        if (!(mo.bound && initialized_)) {
+            AA_HIP(hipMemcpyAsync(mo.rf.verts.p, mo.verts.data(), sizeof(double) * mo.verts.size(), hipMemcpyHostToDevice, s()));
+            AA_HIP(hipStreamSynchronize(s()));
+        }
+        if (!mo.rf.verts_prev.p) mo.rf.verts_prev.alloc(mo.verts.size());
+        mo.carry_fresh = true;
+    }
+    mo.carry = on;
+}
+
+bool ElasticSolver::mesh_obstacle_carry(int mesh_id) const { return mesh_at(mesh_id, "get_mesh_obstacle_carry: ").carry; }
+
 // The pass, on the pair (u, x) the step writes back: with Anderson in the (u, x) variant the
 // un-accelerated pair of the last iteration (default_u, default_x: du_, dx_), otherwise the
 // current one (u_, xfull_). Everything it reads beside the solver's own tables is uploaded here
 // from host snapshots that outlive the copies.
 void ElasticSolver::friction_enqueue(bool accel) {
     fr_ran_ = false;
+    fr_carry_ran_ = false;
     fr_count_ = 0;
     if (!friction_active()) {
         fr_prev_valid_ = false;
@@ -1430,16 +1453,48 @@ void ElasticSolver::friction_enqueue(bool accel) {
         const double* u = def ? du_.p : u_.p;
         const FrictionTables T{fr_obs_prev_.p, fr_mesh_prev_.p, fr_mu_dev_.p, fr_still_.p};
         const ContactRecDev rec{rec_hit_.p, rec_row_.p, rec_c_.p, rec_n_.p, rec_j_.p, rec_rt_.p, rec_s_.p};
+        // carry: the table, and the previous vertices made equal to the ones in force where they
+        // hold no earlier pass's state (carry switched on since, or no pass in the previous step)
+        const bool carry = any_carry();
+        if (carry) {
+            fr_h_carry_.assign(kMaxMeshObstacles, MeshCarryDev{nullptr, nullptr});
+            for (int m = 0; m < nmesh; ++m) {
+                MeshObsBuffers& mo = *meshes_[m];
+                if (!mo.carry) continue;
+                if (mo.carry_fresh || !fr_prev_valid_)
+                    AA_HIP(hipMemcpyAsync(mo.rf.verts_prev.p, mo.rf.verts.p, sizeof(double) * mo.verts.size(), hipMemcpyDeviceToDevice, s()));
+                mo.carry_fresh = false;
+                fr_h_carry_[m] = MeshCarryDev{mo.rf.verts_prev.p, mo.rf.leaf_vid.p};
+            }
+            if (!fr_carry_.p) fr_carry_.alloc(fr_h_carry_.size());
+            AA_HIP(hipMemcpyAsync(fr_carry_.p, fr_h_carry_.data(), fr_h_carry_.size() * sizeof(MeshCarryDev), hipMemcpyHostToDevice, s()));
+            if ((int)rec_tri_.n < fr_count_) { rec_tri_.alloc(fr_count_); rec_b_.alloc(3 * (size_t)fr_count_); }
+        }
+        const ContactFeatDev feat{rec_tri_.p, rec_b_.p};
         if (!fr_ev0_) { AA_HIP(hipEventCreate(&fr_ev0_)); AA_HIP(hipEventCreate(&fr_ev1_)); }
         AA_HIP(hipEventRecord(fr_ev0_, s()));   // kernel_stats("friction"): the pass's device time
         int off = 0;
         for (auto& g : groups_) {
             if (g.d.kind != 2) continue;
-            launch_contact_friction(g.d, xs_.p, xsrc, xfull_.p, u, mass_.p, nf_, st_.penalty, st_.timestep_s, mesh_table(g.d),
-                                    T, rec, off, s());
+            if (carry)
+                launch_contact_friction_carry(g.d, xs_.p, xsrc, xfull_.p, u, mass_.p, nf_, st_.penalty, st_.timestep_s,
+                                              mesh_table(g.d), T, rec, off, fr_carry_.p, feat, s());
+            else
+                launch_contact_friction(g.d, xs_.p, xsrc, xfull_.p, u, mass_.p, nf_, st_.penalty, st_.timestep_s, mesh_table(g.d),
+                                        T, rec, off, s());
             off += g.d.count;
         }
         AA_HIP(hipEventRecord(fr_ev1_, s()));
+        if (carry) {   // the vertices in force now are the next pass's previous ones: device to device, no wait
+            for (int m = 0; m < nmesh; ++m) {
+                MeshObsBuffers& mo = *meshes_[m];
+                if (mo.carry)
+                    AA_HIP(hipMemcpyAsync(mo.rf.verts_prev.p, mo.rf.verts.p, sizeof(double) * mo.verts.size(), hipMemcpyDeviceToDevice, s()));
+            }
+            if (!fr_ev2_) AA_HIP(hipEventCreate(&fr_ev2_));
+            AA_HIP(hipEventRecord(fr_ev2_, s()));   // kernel_stats("carry_copy")
+            fr_carry_ran_ = true;
+        }
     }
     obs_prev_ = obstacles_;
     mesh_rows_prev_ = mesh_rows_;
@@ -1482,6 +1537,28 @@ int ElasticSolver::contacts(int cap, int* node, int* obstacle, double* point3, d
             }
             ++k;
         }
+    }
+    return k;
+}
+
+int ElasticSolver::contact_features(int cap, int* tri, double* bary3) {
+    if (!fr_ran_ || !fr_carry_ran_ || fr_count_ == 0) return 0;
+    const size_t n = (size_t)fr_count_;
+    std::vector<int> hit(n), t(n);
+    std::vector<double> b(3 * n);
+    AA_HIP(hipStreamSynchronize(s()));
+    AA_HIP(hipMemcpy(hit.data(), rec_hit_.p, n * sizeof(int), hipMemcpyDeviceToHost));
+    AA_HIP(hipMemcpy(t.data(), rec_tri_.p, n * sizeof(int), hipMemcpyDeviceToHost));
+    AA_HIP(hipMemcpy(b.data(), rec_b_.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+    int k = 0;
+    for (size_t e = 0; e < n; ++e) {   // the records lie in collision-term order, group after group, as contacts() reads them
+        if (!hit[e]) continue;
+        if (k < cap) {
+            if (tri) tri[k] = t[e];
+            for (int i = 0; i < 3; ++i)
+                if (bary3) bary3[3 * (size_t)k + i] = b[3 * e + i];
+        }
+        ++k;
     }
     return k;
 }
@@ -1652,6 +1729,16 @@ bool ElasticSolver::kernel_stats(const std::string& name, double* avg_ms, double
         float ms = 0;
         AA_HIP(hipEventSynchronize(fr_ev1_));
         AA_HIP(hipEventElapsedTime(&ms, fr_ev0_, fr_ev1_));
+        if (avg_ms) *avg_ms = ms;
+        if (bytes) *bytes = 0;
+        if (launches) *launches = 1;
+        return true;
+    }
+    if (name == "carry_copy") {   // the last step's refresh of the carrying meshes' previous vertices
+        if (!fr_ran_ || !fr_carry_ran_) return false;
+        float ms = 0;
+        AA_HIP(hipEventSynchronize(fr_ev2_));
+        AA_HIP(hipEventElapsedTime(&ms, fr_ev1_, fr_ev2_));
         if (avg_ms) *avg_ms = ms;
         if (bytes) *bytes = 0;
         if (launches) *launches = 1;

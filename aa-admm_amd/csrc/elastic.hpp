@@ -57,6 +57,10 @@ struct MeshObsBuffers {
     bool bound = false;
     std::vector<int> bound_nodes, exempt_nodes;
     DevBuf<unsigned char> exempt;
+    // Carry: the friction pass takes this mesh's displacement from its vertices' own motion
+    // (contact_friction.hpp); carry_fresh = switched on since the last pass, whose previous vertices
+    // are made equal to the ones in force before the next pass reads them
+    bool carry = false, carry_fresh = false;
 };
 
 class ElasticSolver {
@@ -105,6 +109,15 @@ public:
     void set_obstacle_friction(int index, double mu);
     double obstacle_friction(int index) const;
     void record_contacts(bool on);
+    // Carry, per mesh, default off: the pass derives a carrying mesh's displacement at a contact from
+    // its vertices' own motion since the previous step's pass (a deforming or bound mesh then drags
+    // the nodes on it as a posed one does). Before or after initialize, between steps; the graph
+    // stays. A solver in which no mesh carries launches the plain pass. One rank only.
+    void set_mesh_obstacle_carry(int mesh_id, bool on);
+    bool mesh_obstacle_carry(int mesh_id) const;
+    // the last step's contact features, in contacts()'s order: the caller's triangle index (-1 for an
+    // analytic row) and the barycentric weights; 0 when that step's pass was not the carry form
+    int contact_features(int cap, int* tri, double* bary3);
     // the last step's terms in contact, in collision-term order; returns their count (every output
     // optional, at most cap entries written)
     int contacts(int cap, int* node, int* obstacle, double* point3, double* normal3, double* push, double* slip3,
@@ -208,7 +221,16 @@ private:
     DevBuf<unsigned char> fr_still_;
     DevBuf<int> rec_hit_, rec_row_;
     DevBuf<double> rec_c_, rec_n_, rec_j_, rec_rt_, rec_s_;
+    // carry: the table the carry form reads (host snapshot and device copy), its feature records,
+    // and whether the last step's pass was that form
+    std::vector<MeshCarryDev> fr_h_carry_;
+    DevBuf<MeshCarryDev> fr_carry_;
+    DevBuf<int> rec_tri_;
+    DevBuf<double> rec_b_;
+    bool fr_carry_ran_ = false;
+    bool any_carry() const { for (auto& m : meshes_) if (m->carry) return true; return false; }
     hipEvent_t fr_ev0_ = nullptr, fr_ev1_ = nullptr;   // around the pass (kernel_stats("friction"))
+    hipEvent_t fr_ev2_ = nullptr;                      // after the carry snapshot copies (kernel_stats("carry_copy"))
     bool friction_active() const;
     void friction_enqueue(bool accel);
     std::vector<int> pin_order_;

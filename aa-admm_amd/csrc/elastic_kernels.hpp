@@ -51,6 +51,14 @@ struct FrictionTables {
     const double* mu;                 // [rows] coefficient per obstacle row, shared insertion order
     const unsigned char* mesh_still;  // [mesh rows] non-zero: g = 0 (vertices changed, bound mesh)
 };
+// A mesh that carries (aa_elastic_set_mesh_obstacle_carry): one row per mesh row, both null for a
+// mesh that does not. Kept beside FrictionTables, not in it, and handed only to the carry form of
+// the pass as its trailing pack (as GroupVar is): growing FrictionTables would move the plain
+// kernel's arguments.
+struct MeshCarryDev {
+    const double* vprev;     // [nv][3] the vertices in force during the previous step's pass
+    const int* leaf_vid;     // [tris][3] vertex ids of leaf triangle k (MeshRefitTables::leaf_vid)
+};
 __host__ __device__ constexpr int ncol_of(int nv) { return nv > 1 ? nv - 1 : 1; }   // 1 vertex: identity reduction
 
 // Device-side control block: residual bookkeeping, reject/done flags, Anderson state.

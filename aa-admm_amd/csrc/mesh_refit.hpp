@@ -63,6 +63,9 @@ void launch_mesh_bound(const MeshBoundView& b, hipStream_t s);
 struct MeshRefitBuffers {
     DevBuf<int> leaf_vid, node_beg, node_cnt, vt_ptr, vt, edge_tris, big_node, big_chunk_ptr, chunk_big, chunk_beg, chunk_cnt;
     DevBuf<double> verts, fa, partial;
+    // a carrying mesh (aa_elastic_set_mesh_obstacle_carry): the vertices in force during the last
+    // step in which the friction pass ran, refreshed from verts on the device after the pass
+    DevBuf<double> verts_prev;
     PinnedBuf<double> stage;
     int nv = 0, nf = 0;
     // bound obstacles: the caller's triangles, the binding and the check's partials (bind())

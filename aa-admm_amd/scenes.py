@@ -112,6 +112,11 @@ class Scene:
     # (a body is exempt from its own surface). None = no mesh is bound / no node is exempt.
     mesh_obstacle_bindings: Optional[list] = None
     mesh_obstacle_exempt: Optional[list] = None
+    # carry: per mesh, True = the friction pass takes the mesh's displacement at a contact from its
+    # vertices' own motion (capi.solver_from_scene switches it on). None = no mesh carries.
+    mesh_obstacle_carry: Optional[list] = None
+    # (n, 3) node velocities set through set_v after initialize (capi.run_scene); None = at rest
+    initial_velocity: Optional[np.ndarray] = None
     winds: list = dataclasses.field(default_factory=list)
     # Coulomb friction: a coefficient (or None) per obstacle row of the insertion order, `obstacles`
     # first, then `mesh_obstacles` (capi.solver_from_scene); record_contacts keeps the per-term contact
@@ -733,4 +738,83 @@ def block_on_turntable(friction=None, *, dtheta=0.01, cells=(4, 2, 4), cell=0.25
         poses[k, 0, :9] = rotation_y((k + 1) * dtheta).reshape(9)
     sc.mesh_obstacle_poses = poses
     sc.obstacle_friction = None if friction is None else [friction]
+    return sc
+
+
+def _slab(cells, cell):
+    """block_on_turntable's slab: a box, its top face at y = 0."""
+    ext = 2.0 * cell * max(cells[0], cells[2])
+    V = np.array([[x, y, z] for x in (-ext, ext) for y in (-0.5 * ext, 0.0) for z in (-ext, ext)])
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]   # outward
+    return V, np.array([tri for a, b, c, d in quads for tri in ((a, b, c), (a, c, d))], np.int32)
+
+
+def block_on_conveyor_mesh(friction=None, shift=0.01, *, carry=True, cells=(4, 2, 4), cell=0.25, E=1e7, nu=0.3, iters=40,
+                           aa_m=5, accel=1, n_steps=40, dt=1.0 / 60.0, record=True) -> Scene:
+    """The block on block_on_turntable's slab, every vertex of which is translated by `shift` in x
+    per step through the vertex setter (step k runs against the slab moved by k shift): the motion of
+    block_on_moving_floor expressed as a change of shape. With friction and carry the block is
+    carried along; with carry off the pass takes the surface as standing still and the block is
+    braked where it is. Obstacle row 0 is the mesh."""
+    sc = block_on_incline(0.0, None, cells=cells, cell=cell, E=E, nu=nu, iters=iters, aa_m=aa_m, accel=accel,
+                          n_steps=n_steps, dt=dt, record=record)
+    sc.name = "block_on_conveyor_mesh"
+    sc.obstacles = []
+    V, F = _slab(cells, cell)
+    sc.mesh_obstacles = [(V, F)]
+    sc.mesh_obstacle_vertices = [[V + np.array([k * shift, 0.0, 0.0])] for k in range(1, n_steps + 1)]
+    sc.mesh_obstacle_carry = [bool(carry)]
+    sc.obstacle_friction = None if friction is None else [friction]
+    return sc
+
+
+def block_on_twisting_slab(friction=None, dtheta=0.01, *, carry=True, cells=(4, 2, 4), cell=0.25, E=1e7, nu=0.3, iters=40,
+                           aa_m=5, accel=1, n_steps=40, dt=1.0 / 60.0, record=True) -> Scene:
+    """block_on_turntable with the turn expressed through the vertex setter: step k runs against the
+    slab's vertices rotated about y by k dtheta (rotation_y, as the turntable's pose)."""
+    sc = block_on_conveyor_mesh(friction, 0.0, carry=carry, cells=cells, cell=cell, E=E, nu=nu, iters=iters, aa_m=aa_m,
+                                accel=accel, n_steps=n_steps, dt=dt, record=record)
+    sc.name = "block_on_twisting_slab"
+    V = sc.mesh_obstacles[0][0]
+    sc.mesh_obstacle_vertices = [[V @ rotation_y(k * dtheta).T] for k in range(1, n_steps + 1)]
+    return sc
+
+
+def block_on_sliding_block(friction=None, v0=0.6, *, carry=True, cells=(4, 2, 4), cell=0.25, E=1e7, nu=0.3, iters=40, aa_m=5,
+                           accel=1, n_steps=40, dt=1.0 / 60.0, record=True, lower_cells=(8, 1, 8)) -> Scene:
+    """Body on body: a stiff lower block (kuhn_tet_blocks, whose boundary is closed) resting on a
+    FLOOR (row 0, mu = 0) and given the velocity v0 in x (Scene.initial_velocity, which the scene
+    runner applies through set_v); its boundary faces are mesh obstacle 0 (row 1, the coefficient
+    `friction`), bound to its surface nodes, which are exempt from it. The upper block (_block) lies
+    at rest on the lower one's top face; its bottom nodes and the lower block's bottom nodes are the
+    collision terms. With friction and carry the upper block rides along; with carry off it is
+    braked against the world. Lower block nodes come first: they are mesh_obstacle_exempt[0]."""
+    lv, lt = kuhn_tet_blocks(*lower_cells)
+    lv = lv * float(cell)
+    lv = lv - np.array([0.5 * lv[:, 0].max(), 0.0, 0.5 * lv[:, 2].max()])
+    lm = tet_masses(lv, lt, 1522.0)
+    top = lv[:, 1].max()
+    uv, ut, um, ubottom = _block(cells, cell, E, nu)
+    uv = uv + np.array([0.0, top, 0.0])
+    nl = len(lv)
+    faces = tet_boundary_faces(lv, lt)
+    surf = np.unique(faces).astype(np.int32)
+    local = np.full(nl, -1, np.int32)
+    local[surf] = np.arange(len(surf), dtype=np.int32)
+    lbottom = np.nonzero(lv[:, 1] < 1e-3 * cell)[0].astype(np.int32)
+    x = np.concatenate([lv, uv], axis=0)
+    sc = Scene(x=x, masses=np.concatenate([lm, um]),
+               groups=[ElementGroup(TET, LINEAR, E, nu, lt), ElementGroup(TET, LINEAR, E, nu, (ut + nl).astype(np.int32))],
+               pin_idx=np.zeros(0, np.int32), pin_pts=np.zeros((0, 3)), pin_vel=np.zeros((0, 3)), variant=VARIANT_H, dt=dt,
+               iters=iters, aa_m=aa_m, n_steps=n_steps, accel=accel, name="block_on_sliding_block", rest=x.copy())
+    sc.obstacles = [(OBS_FLOOR, (0.0,))]
+    sc.mesh_obstacles = [(lv[surf].copy(), local[faces].astype(np.int32))]
+    sc.mesh_obstacle_bindings = [surf]
+    sc.mesh_obstacle_exempt = [np.arange(nl, dtype=np.int32)]
+    sc.mesh_obstacle_carry = [bool(carry)]
+    sc.collision_idx = np.concatenate([lbottom, ubottom + nl]).astype(np.int32)
+    sc.obstacle_friction = None if friction is None else [0.0, friction]
+    sc.record_contacts = record
+    sc.initial_velocity = np.zeros_like(x)
+    sc.initial_velocity[:nl, 0] = v0
     return sc

@@ -205,7 +205,7 @@ int aa_elastic_get_mesh_obstacle_pose(aa_elastic h, int mesh_id, double pose12[1
  * the call returns; every device buffer and the mesh's table row keep their addresses, so the
  * captured step graph is kept. The vertices hold for every ADMM iteration of every later step until
  * changed. The obstacle stays kinematic; the friction pass (aa_elastic_set_obstacle_friction) takes
- * no displacement from a change of shape. Validation
+ * no displacement from a change of shape unless the mesh carries (aa_elastic_set_mesh_obstacle_carry). Validation
  * happens on the host before anything on the device is touched, and a refused call leaves the
  * obstacle exactly as it was. AA_ERR_ARG, the message naming the cause: an unknown mesh_id, a null
  * pointer, a non-finite coordinate (the vertex named), a zero-area triangle (named; the test of
@@ -225,8 +225,9 @@ int aa_elastic_get_mesh_obstacle_vertices(aa_elastic h, int mesh_id, double* ver
  * unbinding keep the graph.
  * Coupling: the obstacle holds its start-of-step shape for every ADMM iteration of that step --
  * lagged, explicit coupling. The friction pass (aa_elastic_set_obstacle_friction) treats its surface
- * as standing still and applies no reaction to its nodes, and it is refitted once per step, not
- * more often. The BVH is not rebuilt when the shape drifts far from the added one: the
+ * as standing still unless the mesh carries (aa_elastic_set_mesh_obstacle_carry: the surface then
+ * drags the nodes on it with the body's displacement over the previous step) and applies no
+ * reaction to its nodes, and it is refitted once per step, not more often. The BVH is not rebuilt when the shape drifts far from the added one: the
  * cost growth stated above for the vertex setter applies alike.
  * Validity is decided on the device, because the host never sees the gathered shape. The causes
  * are the vertex setter's, tested in this order, the lowest-numbered one reported:
@@ -248,8 +249,8 @@ int aa_elastic_get_mesh_obstacle_vertices(aa_elastic h, int mesh_id, double* ver
  * count, a node index out of range, a mesh that has a pose, a solver partitioned over more than one
  * rank (a rank holds only its part of the nodes: partitioned binding is out of scope).
  * aa_elastic_set_mesh_obstacle_pose and aa_elastic_set_mesh_obstacle_vertices refuse a bound mesh.
- * Not provided: self-collision (see the exemption below), partitioned solvers, friction against the
- * surface's own motion, more than one refit per step, a BVH rebuild on drift, and the z-AA variant, which
+ * Not provided: self-collision (see the exemption below), partitioned solvers, a reaction of the
+ * contact on the body's nodes, more than one refit per step, a BVH rebuild on drift, and the z-AA variant, which
  * refuses collision terms as before. */
 int aa_elastic_bind_mesh_obstacle(aa_elastic h, int mesh_id, const int* nodes, int n_verts);
 int aa_elastic_mesh_obstacle_status(aa_elastic h, int mesh_id, int* bound, int* refits, int* skipped, int* last_cause);
@@ -297,6 +298,27 @@ int aa_elastic_set_obstacle(aa_elastic h, int index, int type, const double* par
  *      whose vertices changed since the previous step (aa_elastic_set_mesh_obstacle_vertices) or
  *      that is bound to solver nodes. In the first step, and in the first step after a step in
  *      which the pass did not run, previous = now.
+ *      A mesh that carries (aa_elastic_set_mesh_obstacle_carry, below) is never taken as standing
+ *      still, whether bound, changed or neither; its g follows its vertices' own motion, with the
+ *      leaf triangle tri the walk of step 2 found c on:
+ *        c_l = c in the obstacle frame of the pose now, as above;
+ *        A, B, C = the corners of tri now; A-, B-, C- = the same three vertices in the vertices in
+ *        force during the previous step's pass;
+ *        e1 = B - A, e2 = C - A, d = c_l - A; d11 = e1.e1, d12 = e1.e2, d22 = e2.e2, p1 = d.e1,
+ *        p2 = d.e2, every dot (a0 b0 + a1 b1) + a2 b2; den = d11 d22 - d12 d12;
+ *        b1 = (d22 p1 - d12 p2) / den, b2 = (d11 p2 - d12 p1) / den, b0 = (1 - b1) - b2;
+ *        b = (1, 0, 0) if !(den > 0);
+ *        g_l = (b0 (A - A-) + b1 (B - B-)) + b2 (C - C-) componentwise, p_l = c_l - g_l,
+ *        g = c - ((R_prev p_l) + t_prev).
+ *      The displacement form, not a difference of interpolated positions: with unchanged vertices
+ *      every corner difference is an exact zero, p_l = c_l and g is the rigid expression bit for
+ *      bit; and the interpolation is continuous across shared edges and vertices, so which of two
+ *      tying triangles the walk returns does not matter beyond rounding. The state "during the
+ *      previous step" is the pose path's notion: for a vertex setter's mesh the vertices set before
+ *      that step, for a bound mesh the body's start-of-step shape then -- so a bound mesh carries
+ *      with the body's displacement over the previous step, lagged and explicit like the rest of
+ *      that coupling, and a skipped refit leaves the vertices as they were (g_l = 0). Previous =
+ *      now in the first step, after a step without the pass, and when carry was switched on since.
  *   6  rel = (x_new - x_old) - g, rn = (rel0 n0 + rel1 n1) + rel2 n2, rt = rel - rn n,
  *      lt = sqrt((rt0^2 + rt1^2) + rt2^2); s = 0 if mu_r == 0, j == 0 or !(lt > 0), else
  *      min(1, (mu_r j) / lt); x_new -= s rt, written only when s != 0.
@@ -305,8 +327,9 @@ int aa_elastic_set_obstacle(aa_elastic h, int index, int type, const double* par
  * A collision term on a pinned node is reported but never filtered.
  * What it is not: the friction is lagged and explicit, applied once per step with the normal force
  * of the solve just finished -- it is not part of the ADMM iteration; there is no rolling or
- * anisotropic friction, no friction from a deforming or bound mesh's own surface motion, and no
- * reaction on a bound obstacle's nodes.
+ * anisotropic friction, and no reaction on a bound obstacle's nodes. A deforming or bound mesh's
+ * own surface motion enters only for a mesh that carries; partitioned solvers and the z-AA variant
+ * (which refuses collision terms) are not served.
  * aa_elastic_record_contacts(on) keeps the pass running for its records even with every mu = 0.
  * aa_elastic_get_contacts returns the last step's terms in contact, in collision-term order: *n
  * their full count, at most cap entries in each given array (every array may be NULL) -- the node
@@ -321,6 +344,25 @@ int aa_elastic_get_obstacle_friction(aa_elastic h, int index, double* mu);
 int aa_elastic_record_contacts(aa_elastic h, int on);
 int aa_elastic_get_contacts(aa_elastic h, int cap, int* n, int* node, int* obstacle, double* point3, double* normal3,
                             double* push, double* slip3, double* scale);
+/* Carry, per mesh obstacle, default off: the friction pass takes the mesh's displacement at a
+ * contact from its vertices' own motion (step 5 above), so a surface moved through
+ * aa_elastic_set_mesh_obstacle_vertices or bound to solver nodes drags the nodes on it as one moved
+ * through its pose does. May be switched before or after initialize and between steps; the captured
+ * step graph is kept, because the pass is outside it. A mesh with carry off behaves exactly as
+ * before, and a solver in which no mesh carries launches the pass it always launched and computes
+ * bit for bit what it did; with some mesh carrying, the pass runs in its carry form for every row.
+ * The previous vertices are one more device buffer per carrying mesh, refreshed by a device-to-
+ * device copy on the solver's stream after the pass: no host copy, no wait.
+ * aa_elastic_get_contact_features returns, in the order of aa_elastic_get_contacts, the triangle
+ * (the caller's index; -1 for an analytic row) and the barycentric weights b of step 5 for the
+ * last step's contacts, filled for every mesh-row contact, carrying mesh or not: *n their count, at
+ * most cap entries per array (either may be NULL); *n = 0 when the last step's pass was not the
+ * carry form.
+ * AA_ERR_ARG: an unknown mesh_id, a null output (on, n), and switching on after initialize in a
+ * solver partitioned over more than one rank. */
+int aa_elastic_set_mesh_obstacle_carry(aa_elastic h, int mesh_id, int on);
+int aa_elastic_get_mesh_obstacle_carry(aa_elastic h, int mesh_id, int* on);
+int aa_elastic_get_contact_features(aa_elastic h, int cap, int* n, int* tri, double* bary3);
 /* Solver::set_collisions(inds, points) (admm_anderson_hard_zxu/src/Solver.cpp:318-344): one
  * Collision energy term (CollisionEnergyTerm.hpp:41-117: identity reduction, weight
  * sqrt(2 k(soft rubber)), prox = closest obstacle surface point when inside one) per listed node,
@@ -547,7 +589,10 @@ int aa_geom_set_comm(aa_geom h, aa_comm c);
  *     concatenated meshes with poses now and previous (12 doubles per mesh, a row of NaNs = no
  *     pose) and mesh_still (optional; non-zero = g is 0 for that mesh); per query the exemption
  *     node id, a pinned flag, x_old, x_new, u, w, m; p and dt. Outputs per query: x' (x_new's bits
- *     where s = 0), the contact flag, the row, c, n, j, rt, s. */
+ *     where s = 0), the contact flag, the row, c, n, j, rt, s.
+ *   aa_test_contact_friction_carry: the carry form of the same on the same arguments plus, per
+ *     mesh, the previous vertices (concatenated like mesh_verts3) and a carry flag; it also returns
+ *     per query the triangle (the caller's index, -1 = none) and the barycentric weights. */
 int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double* in, int n, double* out, int* iters);
 int aa_test_cod_solve(aa_ctx ctx, int k, const double* M, const double* b, double* theta);
 int aa_test_geom_project(aa_ctx ctx, int type, int k, const double* prm2, const double* in, int n, double* out);
@@ -583,6 +628,15 @@ int aa_test_contact_friction(aa_ctx ctx, const double* obs_rows, const double* o
                              const double* x_old3, const double* x_new3, const double* u3, const double* w,
                              const double* m, double penalty, double dt, double* x_out3, int* hit, int* row,
                              double* point3, double* normal3, double* push, double* slip3, double* scale);
+int aa_test_contact_friction_carry(aa_ctx ctx, const double* obs_rows, const double* obs_rows_prev, const double* mu, int n_obs,
+                                   const double* mesh_verts3, const int* mesh_vert_ptr, const int* mesh_tris3,
+                                   const int* mesh_tri_ptr, int n_meshes, const double* mesh_poses,
+                                   const double* mesh_poses_prev, const unsigned char* mesh_still, const int* q_node,
+                                   const unsigned char* q_pinned, int n, const int* exempt_ptr, const int* exempt_nodes,
+                                   const double* x_old3, const double* x_new3, const double* u3, const double* w,
+                                   const double* m, double penalty, double dt, const double* mesh_verts_prev3,
+                                   const unsigned char* mesh_carry, double* x_out3, int* hit, int* row, double* point3,
+                                   double* normal3, double* push, double* slip3, double* scale, int* tri, double* bary3);
 /* The global step's sparse triangular solve alone (DirectSolver, csrc/direct_solve.hpp), on a
  * caller-given SPD matrix: full-pattern symmetric CSR (ptr, col, val; sorted columns, every
  * diagonal stored) of order n in the caller's ordering, node coordinates xyz3.

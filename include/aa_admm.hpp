@@ -361,6 +361,19 @@ public:
         check(aa_elastic_get_obstacle_friction(h_, row, &mu));
         return mu;
     }
+    // Carry (aa_admm.h, aa_elastic_set_mesh_obstacle_carry), per mesh, default off: the friction pass
+    // takes the mesh's displacement at a contact from its vertices' own motion, so a mesh moved
+    // through set_obstacle_vertices or bound to a body drags the nodes on it as a posed one does.
+    void set_obstacle_carry(const std::shared_ptr<PassiveMesh>& mesh, bool on = true) {
+        if (!mesh || mesh->mesh_id < 0 || row_of(mesh.get()) < 0) throw std::runtime_error("set_obstacle_carry: the mesh was not added to this solver");
+        check(aa_elastic_set_mesh_obstacle_carry(h_, mesh->mesh_id, on ? 1 : 0));
+    }
+    bool obstacle_carry(const std::shared_ptr<PassiveMesh>& mesh) const {
+        if (!mesh || mesh->mesh_id < 0 || row_of(mesh.get()) < 0) throw std::runtime_error("obstacle_carry: the mesh was not added to this solver");
+        int on = 0;
+        check(aa_elastic_get_mesh_obstacle_carry(h_, mesh->mesh_id, &on));
+        return on != 0;
+    }
     void record_contacts(bool on = true) { check(aa_elastic_record_contacts(h_, on ? 1 : 0)); }
     // the last step's collision terms in contact, in term order
     struct Contact {
