@@ -23,7 +23,7 @@ EXPORTS = [
     "aa_last_error", "aa_version", "aa_ctx_create", "aa_ctx_destroy", "aa_ctx_synchronize", "aa_ctx_bench_read",
     "aa_ctx_warm_dense", "aa_lame_from_young",
     "aa_settings_default", "aa_elastic_create", "aa_elastic_destroy", "aa_elastic_add_nodes", "aa_elastic_add_tets",
-    "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
+    "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_add_bending", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
     "aa_elastic_add_obstacle", "aa_elastic_add_mesh_obstacle", "aa_elastic_set_mesh_obstacle_pose",
     "aa_elastic_get_mesh_obstacle_pose", "aa_elastic_set_mesh_obstacle_vertices", "aa_elastic_get_mesh_obstacle_vertices",
     "aa_elastic_bind_mesh_obstacle", "aa_elastic_mesh_obstacle_status", "aa_elastic_set_mesh_obstacle_exempt",
@@ -336,6 +336,17 @@ class Solver:
         la = self._lame_array(len(t) // 3, mu, lam, limit_min, limit_max)
         _chk(lib().aa_elastic_add_tris_var(self.h, _dp(v), _ip(t), C.c_int(len(t) // 3),
                                            la.ctypes.data_as(C.POINTER(Lame)), C.c_int(vertex_offset)))
+
+    def add_bending(self, verts, tris, k_bend, flat_rest=True, vertex_offset=0):
+        """Bending hinges on the interior edges of a triangle list (aa_elastic_add_bending): rest
+        shape verts[tris], stiffness k_bend; flat_rest False keeps the rest shape's curvature as the
+        equilibrium. Before initialize. Returns the hinge count."""
+        v = np.ascontiguousarray(verts, np.float64).reshape(-1)
+        t = np.ascontiguousarray(tris, np.int32).reshape(-1)
+        k = C.c_int()
+        _chk(lib().aa_elastic_add_bending(self.h, _dp(v), _ip(t), C.c_int(len(t) // 3), C.c_double(k_bend),
+                                          C.c_int(1 if flat_rest else 0), C.c_int(vertex_offset), C.byref(k)))
+        return k.value
 
     def set_pins(self, inds, points=None):
         i = np.ascontiguousarray(inds, np.int32).reshape(-1)
@@ -652,6 +663,8 @@ def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
             s.add_tets(scene.rest_x, g.idx, g.material, lame)
         else:
             s.add_tris(scene.rest_x, g.idx, lame)
+    for tris, k_bend, flat_rest in getattr(scene, "bending", None) or []:   # after the groups
+        s.add_bending(scene.rest_x, tris, k_bend, flat_rest)
     s.set_pins(scene.pin_idx, scene.pin_pts)
     for kind, prm in getattr(scene, "obstacles", []):
         s.add_obstacle(kind, prm)
@@ -933,11 +946,13 @@ def run_geom(ctx: Context, sc, comm=None):
 
 def hook_prox(ctx: Context, op, prm4, X):
     """op 0 linear tet, 1 NeoHookean, 2 StVK (prm4 = E, nu, h), 3 / 4 tri H / X prox (prm4[2:] =
-    limits); X (n, 9|6). Returns (out, L-BFGS iterations)."""
+    limits), 5 the bending hinge's prox (prm4[0] = r); X (n, 9|6|3). Returns (out, L-BFGS iterations)."""
     X = np.ascontiguousarray(X, np.float64)
     n = X.shape[0]
     out, it = np.zeros_like(X), np.zeros(n, np.int32)
-    p = np.ascontiguousarray(prm4, np.float64)
+    p = np.zeros(4)
+    q = np.asarray(prm4, np.float64).reshape(-1)
+    p[:len(q)] = q
     _chk(lib().aa_test_prox(ctx.h, C.c_int(op), _dp(p), _dp(X), C.c_int(n), _dp(out), _ip(it)))
     return out, it
 

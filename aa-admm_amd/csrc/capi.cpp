@@ -180,6 +180,15 @@ int aa_elastic_add_tris_var(aa_elastic h, const double* verts3, const int* tris3
     });
 }
 
+int aa_elastic_add_bending(aa_elastic h, const double* verts3, const int* tris3, int n_tris, double k_bend,
+                           int flat_rest, int vertex_offset, int* n_hinges) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        const int k = h->s->add_bending(verts3, tris3, n_tris, k_bend, flat_rest != 0, vertex_offset);
+        if (n_hinges) *n_hinges = k;
+    });
+}
+
 int aa_elastic_set_pins(aa_elastic h, const int* inds, const double* pts3, int n) {
     return guarded([&] { NEED(h, "null handle"); h->s->set_pins(inds, pts3, n); });
 }
@@ -659,11 +668,12 @@ int with_device_arrays(aa_ctx ctx, F&& f) {
 
 extern "C" int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double* in, int n, double* out, int* iters) {
     return with_device_arrays(ctx, [&](hipStream_t s) {
-        NEED(prm4 && in && out && n >= 0 && op >= 0 && op <= 4, "aa_test_prox: bad argument");
-        const int D = op >= 3 ? 6 : 9;
+        NEED(prm4 && in && out && n >= 0 && op >= 0 && op <= 5, "aa_test_prox: bad argument");
+        const int D = op == 5 ? 3 : op >= 3 ? 6 : 9;
         aa::DevBuf<double> di, dout((size_t)D * std::max(n, 1));
         aa::DevBuf<int> dit(std::max(n, 1));
         di.upload(in, (size_t)D * n, s);
+        if (op == 5) AA_HIP(hipMemsetAsync(dit.p, 0, sizeof(int) * std::max(n, 1), s));   // closed form: no iterations
         aa::launch_test_prox(op, prm4, di.p, n, dout.p, dit.p, s);
         AA_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * D * n, hipMemcpyDeviceToHost, s));
         if (iters) AA_HIP(hipMemcpyAsync(iters, dit.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));

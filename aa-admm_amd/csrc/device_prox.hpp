@@ -27,6 +27,16 @@ namespace dev {
 
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
+// ------------------------------------------------------------------ bending hinges (3x1)
+// U(z) = 1/2 kappa (|z| - r)^2 with the ADMM weight w^2 = kappa (bending.hpp): the minimiser of
+// U(z) + 1/2 w^2 |z - v|^2 lies along v at length (|v| + r) / 2, i.e. z = s v with
+// s = 1/2 + 1/2 (r / |v|). v = 0 has no direction: z = v (stated, not derived; r = 0 gives the same).
+__device__ __forceinline__ void hinge_prox(const double* v, double r, double* out) {
+    const double n = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    const double s = n == 0.0 ? 1.0 : 0.5 + 0.5 * (r / n);
+    out[0] = s * v[0]; out[1] = s * v[1]; out[2] = s * v[2];
+}
+
 // ------------------------------------------------------------------ triangles (3x2)
 // z: column-major 3x2 (z[c*3+r]); mode 1 = UX (hard_zxu), 0 = Z (xzu)
 __device__ __forceinline__ void tri_prox(const double* z, double* out, int mode, double lmin, double lmax) {

@@ -146,6 +146,35 @@ void ElasticSolver::add_elements(int kind, int material, const double* verts3, c
     hgroups_.push_back(std::move(g));
 }
 
+// Bending hinges of a triangle list (bending.hpp): one group of kind 3, four vertices and the one
+// column z = K x per hinge, w = sqrt(kappa); the rest length r rides in `vol`.
+int ElasticSolver::add_bending(const double* verts3, const int* tris3, int n_tris, double k_bend, bool flat_rest,
+                               int vertex_offset) {
+    if (initialized_) throw Error(ERR_STATE, "add_bending: adding energy terms after initialize is not supported");
+    // the rest shape is verts3[tris3], the nodes tris3 + vertex_offset: an index is in range when its node exists
+    const HingeSet H = build_hinges(verts3, num_nodes() - vertex_offset, tris3, n_tris, k_bend, flat_rest);
+    const int count = H.count();
+    for (int t = 0; t < n_tris; ++t)
+        for (int a = 0; a < 3; ++a)
+            if (tris3[3 * (size_t)t + a] + vertex_offset < 0)
+                throw Error(ERR_ARG, "add_bending: triangle " + std::to_string(t) + " has a vertex index out of range");
+    HostGroup g;
+    g.kind = 3; g.material = AA_LINEAR; g.lame = aa_lame{};
+    g.nv = 4; g.ncol = 1;
+    g.idx.resize((size_t)count * 4);
+    for (size_t i = 0; i < g.idx.size(); ++i) g.idx[i] = H.idx[i] + vertex_offset;
+    g.G = H.K;
+    g.vol = H.r;
+    g.w.resize(count);
+    for (int e = 0; e < count; ++e) {
+        g.w[e] = std::sqrt(H.kappa[e]);
+        if (!(g.w[e] > 0.0) || !std::isfinite(g.w[e]))
+            throw Error(ERR_NUMERIC, "add_bending: hinge " + std::to_string(e) + " has a weight that is not positive and finite");
+    }
+    hgroups_.push_back(std::move(g));
+    return count;
+}
+
 void ElasticSolver::HostGroup::append_element(const HostGroup& from, size_t t) {
     idx.insert(idx.end(), from.idx.begin() + t * nv, from.idx.begin() + (t + 1) * nv);
     G.insert(G.end(), from.G.begin() + t * ncol * nv, from.G.begin() + (t + 1) * ncol * nv);
@@ -504,6 +533,11 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
         throw Error(ERR_ARG, "initialize: obstacle friction or contact recording is on and the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (a rank holds only its part of the collision terms; friction needs one rank)");
     if (comm_ && comm_->size() > 1 && any_bound())
         throw Error(ERR_ARG, "initialize: a mesh obstacle is bound to solver nodes and the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (bound obstacles need one rank)");
+    const bool bending = std::any_of(hgroups_.begin(), hgroups_.end(), [](const HostGroup& g) { return g.kind == 3; });
+    if (bending && st_.variant == AA_VARIANT_Z)
+        throw Error(ERR_ARG, "initialize: bending hinges exist in the (u,x) variant only (the z variant's gradient step has no hinge term)");
+    if (bending && comm_ && comm_->size() > 1)
+        throw Error(ERR_ARG, "initialize: the solver has bending hinges and is partitioned over " + std::to_string(comm_->size()) + " ranks (bending needs one rank)");
     if (st_.variant == AA_VARIANT_Z && !coll_nodes_.empty())
         throw Error(ERR_ARG, "set_collisions: energy-based collisions exist in the (u,x) variant only (admm_anderson_hard_zxu)");
     // collision terms (Solver.cpp:386-392): after the other terms, one per node in node order;
@@ -932,6 +966,7 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
         const double per = 4.0 * g.d.nv + 8.0 * g.d.ncol * g.d.nv + 8.0;
         lz += g.d.count * (per + 2 * 8.0 * g.d.dim + 28.0 * g.d.nv);   // u in, z out, slot positions + slots out
         if (g.var) lz += g.d.count * (g.d.kind == 1 ? 16.0 : g.d.mat != 0 ? 24.0 : 0.0);   // per-element materials
+        if (g.d.kind == 3) lz += g.d.count * 8.0;   // a hinge's rest length
         rs += g.d.count * (per + 3 * 8.0 * g.d.dim);
     }
     kstats_["local_z"].bytes = lz + 24.0 * n;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/aa_admm.h"
+#include "bending.hpp"
 #include "comm.hpp"
 #include "common.hpp"
 #include "contact_friction.hpp"
@@ -72,6 +73,8 @@ public:
     // per_element given: [count] Lame parameters, one per element (aa_elastic_add_*_var); `lame` is then unused
     void add_elements(int kind, int material, const double* verts3, const int* idx, int count, const aa_lame& lame,
                       int vertex_offset, const aa_lame* per_element = nullptr);
+    // bending hinges on the interior edges of a triangle list (bending.hpp); returns their count
+    int add_bending(const double* verts3, const int* tris3, int n_tris, double k_bend, bool flat_rest, int vertex_offset);
     void set_pins(const int* inds, const double* pts3, int n);
     // energy-based collisions of the (u,x) variant (admm_anderson_hard_zxu Solver.cpp:318-348)
     void add_obstacle(int type, const double* params);
@@ -151,7 +154,7 @@ public:
 
 private:
     struct HostGroup {
-        int kind, material, nv, ncol;
+        int kind, material, nv, ncol;   // kind 3 (bending hinge): G holds K, vol the rest length r
         aa_lame lame;
         std::vector<int> idx;       // [count][nv] global node ids
         std::vector<double> G;      // [count][ncol][nv]

@@ -84,10 +84,10 @@ __device__ __forceinline__ bool gated(const Ctrl* c, int gate_reject) {
 }
 
 // F = P x_full, Cp = P_pinned x_pin  (EnergyTerm::update_z's D.block*x, Solver.cpp C_fix)
-template <int NV>
+template <int S>
 __device__ __forceinline__ void gather_F(const GroupDev& g, int e, const double* __restrict__ xfull, int nf, double* F,
                                          double* Cp) {
-    constexpr int NC = ncol_of(NV);
+    constexpr int NV = shape_nv(S), NC = shape_nc(S);
 #pragma unroll
     for (int i = 0; i < 3 * NC; ++i) { F[i] = 0; Cp[i] = 0; }
 #pragma unroll
@@ -107,21 +107,21 @@ __device__ __forceinline__ void gather_F(const GroupDev& g, int e, const double*
 // Cp alone, for the callers that need only C_fix (the rhs slots after the gradient pass): a group without pinned nodes (g.pinned = 0, kernel-uniform) has Cp = 0 and loads
 // no position; otherwise gather_F's products (F unused). A per-node `if pinned` branch instead was
 // measured slower (the node id load then waits before anything else issues): C4 local_z 412 -> 430 us.
-template <int NV>
+template <int S>
 __device__ __forceinline__ void gather_Cp(const GroupDev& g, int e, const double* __restrict__ xfull, int nf, double* Cp) {
-    constexpr int NC = ncol_of(NV);
+    constexpr int NC = shape_nc(S);
     if (!g.pinned) {
 #pragma unroll
         for (int i = 0; i < 3 * NC; ++i) Cp[i] = 0;
         return;
     }
     double F[3 * NC];
-    gather_F<NV>(g, e, xfull, nf, F, Cp);
+    gather_F<S>(g, e, xfull, nf, F, Cp);
 }
 
-template <int NV>
+template <int S>
 __device__ __forceinline__ void gather_P(const GroupDev& g, int e, const double* __restrict__ xfull, double* F) {
-    constexpr int NC = ncol_of(NV);
+    constexpr int NV = shape_nv(S), NC = shape_nc(S);
 #pragma unroll
     for (int i = 0; i < 3 * NC; ++i) F[i] = 0;
 #pragma unroll
@@ -161,10 +161,10 @@ __device__ __forceinline__ void write_slots_pre(const int* pos, const double* gk
         o[0] = f0; o[1] = f1; o[2] = f2;
     }
 }
-template <int NV>
+template <int S>
 __device__ __forceinline__ void write_slots(const GroupDev& g, int e, int nf, double w, const double* zz,
                                             const double* Cp, const double* uu, double* __restrict__ y) {
-    constexpr int NC = ncol_of(NV);
+    constexpr int NV = shape_nv(S), NC = shape_nc(S);
     double yc[3 * NC];
 #pragma unroll
     for (int i = 0; i < 3 * NC; ++i) yc[i] = w * (w * zz[i] - w * Cp[i] - uu[i]);
@@ -231,7 +231,7 @@ struct LaneMat<true> {
 };
 
 // ------------------------------------------------------------------ local step
-template <int NV, int HYPER, class... V>
+template <int S, int HYPER, class... V>
 __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __restrict__ xfull,
                                                     const double* __restrict__ u, double* __restrict__ z,
                                                     double* __restrict__ y, int nf, int variant, int mode, Ctrl* ctrl,
@@ -239,13 +239,15 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
     constexpr bool VAR = kVar<V...>;
     if (mode != LZ_INIT && gated(ctrl, mode == LZ_REDO)) return;
     __shared__ double sm[kBlock / 64];
-    constexpr int NC = ncol_of(NV), D = 3 * NC;
+    constexpr int NV = shape_nv(S), NC = shape_nc(S), D = 3 * NC;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     double part = 0;
     if (e < g.count) {
         double F[D], Cp[D], uu[D], vin[D], zz[D];
-        gather_F<NV>(g, e, xfull, nf, F, Cp);
+        gather_F<S>(g, e, xfull, nf, F, Cp);
         const double w = g.w[e];
+        double rest = 0.0;   // the hinge's r, with the other loads
+        if constexpr (S == kShapeHinge) rest = g.vol[e];
         load_u<D>(g, e, u, uu);
 #pragma unroll
         for (int i = 0; i < D; ++i) vin[i] = F[i] + uu[i] / w;
@@ -259,6 +261,8 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
         } else if constexpr (NV == 3) {
             if constexpr (VAR) dev::tri_prox(vin, zz, variant, var_of(gvp...).lmin[e], var_of(gvp...).lmax[e]);
             else dev::tri_prox(vin, zz, variant, g.lmin, g.lmax);
+        } else if constexpr (S == kShapeHinge) {
+            dev::hinge_prox(vin, rest, zz);
         } else if constexpr (HYPER == 0) {
             dev::tet_linear_prox(vin, zz);
         } else {
@@ -279,7 +283,7 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
             part += r * r;
             z[g.zoff + (size_t)i * g.count + e] = zz[i];
         }
-        if (y) write_slots<NV>(g, e, nf, w, zz, Cp, uu, y);
+        if (y) write_slots<S>(g, e, nf, w, zz, Cp, uu, y);
     }
     if (red) {
         const double s = block_sum(part, sm);
@@ -772,20 +776,20 @@ __global__ __launch_bounds__(kBlock, 2) void k_local_z_hq2(GroupDev g, const dou
 }
 
 // r = w(P x - z): prim2 += |r|^2, dual2 += |w P (x - x_last)|^2, u += r
-template <int NV>
+template <int S>
 __global__ __launch_bounds__(kBlock) void k_resid_u(GroupDev g, const double* __restrict__ xfull,
                                                     const double* __restrict__ xlast, const double* __restrict__ z,
                                                     double* __restrict__ u, int nf, Ctrl* ctrl, double* red_a,
                                                     double* red_b, int red_off) {
     if (gated(ctrl, 0)) return;
     __shared__ double sm[kBlock / 64];
-    constexpr int NC = ncol_of(NV), D = 3 * NC;
+    constexpr int D = 3 * shape_nc(S);
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     double pa = 0, pb = 0;
     if (e < g.count) {
         double F[D], Fl[D];
-        gather_P<NV>(g, e, xfull, F);
-        gather_P<NV>(g, e, xlast, Fl);
+        gather_P<S>(g, e, xfull, F);
+        gather_P<S>(g, e, xlast, Fl);
         const double w = g.w[e];
 #pragma unroll
         for (int i = 0; i < D; ++i) {
@@ -806,14 +810,15 @@ __global__ __launch_bounds__(kBlock) void k_resid_u(GroupDev g, const double* __
 // uin: the u that modes 0 and 2 read (mode 1 reads none); u: where modes 0 and 1 write it. The two
 // are the same buffer unless u alternates between the parity buffers of the concurrent pass
 // (ElasticSolver::u_at), so neither is __restrict__; each thread reads its entries before it writes them.
-template <int NV, int HYPER, class... V>
+template <int S, int HYPER, class... V>
 __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __restrict__ xfull,
                                                     const double* __restrict__ z, const double* uin, double* u,
                                                     double* __restrict__ y, int nf, int mode, int redo, Ctrl* ctrl,
                                                     V... gvp) {
     constexpr bool VAR = kVar<V...>;
     if (gated(ctrl, redo)) return;
-    constexpr int NC = ncol_of(NV), D = 3 * NC;
+    // (a hinge counts as a shape of its own below: NV is 0 for it, none of the simplex branches)
+    constexpr int NV = S == kShapeHinge ? 0 : shape_nv(S), D = 3 * shape_nc(S);
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= g.count) return;
     // the gradient (mode 1) needs only z: it runs before the element's gathers, so its
@@ -835,8 +840,9 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
     }
     if (mode == 1) {
         double gr[D];
-        if constexpr (NV == 3 || NV == 1) {
-            // TriEnergyTerm::get_gradient / Collision::get_gradient throw in the reference
+        if constexpr (NV == 3 || NV == 1 || S == kShapeHinge) {
+            // TriEnergyTerm::get_gradient / Collision::get_gradient throw in the reference; a hinge
+            // group is refused in the Z variant (initialize), so mode 1 never reaches it
             if (ctrl) ctrl->fail = 2;
 #pragma unroll
             for (int i = 0; i < D; ++i) gr[i] = 0;
@@ -851,32 +857,32 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
         for (int i = 0; i < D; ++i) uu[i] = gr[i] / w;
     }
     if (mode == 0) {
-        gather_F<NV>(g, e, xfull, nf, F, Cp);
+        gather_F<S>(g, e, xfull, nf, F, Cp);
 #pragma unroll
         for (int i = 0; i < D; ++i) uu[i] += w * F[i] - w * zz[i];
     } else {
-        gather_Cp<NV>(g, e, xfull, nf, Cp);
+        gather_Cp<S>(g, e, xfull, nf, Cp);
     }
     if (mode != 2) {
 #pragma unroll
         for (int i = 0; i < D; ++i) u[g.zoff + (size_t)i * g.count + e] = uu[i];
     }
-    write_slots<NV>(g, e, nf, w, zz, Cp, uu, y);
+    write_slots<S>(g, e, nf, w, zz, Cp, uu, y);
 }
 
-template <int NV>
+template <int S>
 __global__ __launch_bounds__(kBlock) void k_prim_z(GroupDev g, const double* __restrict__ xfull,
                                                    const double* __restrict__ z, const double* __restrict__ zref,
                                                    int nf, int redo, Ctrl* ctrl, double* red_a, double* red_b,
                                                    int red_off) {
     if (gated(ctrl, redo)) return;
     __shared__ double sm[kBlock / 64];
-    constexpr int NC = ncol_of(NV), D = 3 * NC;
+    constexpr int D = 3 * shape_nc(S);
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     double pa = 0, pb = 0;
     if (e < g.count) {
         double F[D];
-        gather_P<NV>(g, e, xfull, F);
+        gather_P<S>(g, e, xfull, F);
         const double w = g.w[e];
         double zi[D], zr[D];   // all loads first (a load under `if (zref)` waited per entry)
 #pragma unroll
@@ -915,13 +921,13 @@ __global__ __launch_bounds__(kBlock) void k_prim_sum(GroupDev g, const double* _
     if (threadIdx.x == 0) { red_a[red_off + blockIdx.x] = sa; red_b[red_off + blockIdx.x] = sb; }
 }
 
-template <int NV>
+template <int S>
 __global__ __launch_bounds__(kBlock) void k_init_z(GroupDev g, const double* __restrict__ xfull, double* __restrict__ z) {
-    constexpr int NC = ncol_of(NV), D = 3 * NC;
+    constexpr int D = 3 * shape_nc(S);
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= g.count) return;
     double F[D];
-    gather_P<NV>(g, e, xfull, F);
+    gather_P<S>(g, e, xfull, F);
 #pragma unroll
     for (int i = 0; i < D; ++i) z[g.zoff + (size_t)i * g.count + e] = F[i];
 }
@@ -1763,6 +1769,17 @@ __global__ void k_test_prox(int op, double E, double nu, double p2, double p3, c
     if (iters) iters[e] = it;
 }
 
+// op 5: the hinge prox (3 in / out per hinge, prm[0] = r)
+__global__ __launch_bounds__(kBlock) void k_test_hinge_prox(double r, const double* __restrict__ in, int n,
+                                                            double* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const double v[3] = {in[3 * (size_t)e], in[3 * (size_t)e + 1], in[3 * (size_t)e + 2]};
+    double z[3];
+    dev::hinge_prox(v, r, z);
+    for (int i = 0; i < 3; ++i) out[3 * (size_t)e + i] = z[i];
+}
+
 // aa_test_mesh_sdf: the production mesh_signed_distance decides `inside` (root-box cull included);
 // a query it turns away is walked all the same for the report (c, +|q - c|, triangle)
 __global__ __launch_bounds__(kBlock) void k_test_mesh_sdf(const MeshObsDev* __restrict__ mesh, const double* __restrict__ q,
@@ -1889,7 +1906,8 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
         AA_CHECK_LAUNCH();
         return;
     }
-    if (g.kind == 2 && meshes) hipLaunchKernelGGL((k_local_z<1, 0, const MeshObsDev*>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, meshes);
+    if (g.kind == 3) hipLaunchKernelGGL((k_local_z<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+    else if (g.kind == 2 && meshes) hipLaunchKernelGGL((k_local_z<1, 0, const MeshObsDev*>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, meshes);
     else if (g.kind == 2) hipLaunchKernelGGL((k_local_z<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
     else if (g.kind == 1 && var) hipLaunchKernelGGL((k_local_z<3, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, var);
     else if (g.kind == 1) hipLaunchKernelGGL((k_local_z<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
@@ -1927,7 +1945,8 @@ void launch_resid_update_u(const GroupDev& g, const double* xfull, const double*
                            int nf, Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 2) hipLaunchKernelGGL(k_resid_u<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+    if (g.kind == 3) hipLaunchKernelGGL(k_resid_u<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+    else if (g.kind == 2) hipLaunchKernelGGL(k_resid_u<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
     else if (g.kind == 1) hipLaunchKernelGGL(k_resid_u<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
     else hipLaunchKernelGGL(k_resid_u<4>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
     AA_CHECK_LAUNCH();
@@ -1937,7 +1956,8 @@ void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, con
                     int nf, int mode, int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 2) hipLaunchKernelGGL((k_u_and_y<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+    if (g.kind == 3) hipLaunchKernelGGL((k_u_and_y<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+    else if (g.kind == 2) hipLaunchKernelGGL((k_u_and_y<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
     else if (g.kind == 1) hipLaunchKernelGGL((k_u_and_y<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);   // no material reads
     else if (g.mat == 0 && var) hipLaunchKernelGGL((k_u_and_y<4, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl, var);
     else if (g.mat == 0) hipLaunchKernelGGL((k_u_and_y<4, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
@@ -1950,7 +1970,8 @@ void launch_prim_z(const GroupDev& g, const double* xfull, const double* z, cons
                    Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 2) hipLaunchKernelGGL(k_prim_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+    if (g.kind == 3) hipLaunchKernelGGL(k_prim_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+    else if (g.kind == 2) hipLaunchKernelGGL(k_prim_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
     else if (g.kind == 1) hipLaunchKernelGGL(k_prim_z<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
     else hipLaunchKernelGGL(k_prim_z<4>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
     AA_CHECK_LAUNCH();
@@ -1959,7 +1980,8 @@ void launch_prim_z(const GroupDev& g, const double* xfull, const double* z, cons
 void launch_init_z(const GroupDev& g, const double* xfull, double* z, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 2) hipLaunchKernelGGL(k_init_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+    if (g.kind == 3) hipLaunchKernelGGL(k_init_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+    else if (g.kind == 2) hipLaunchKernelGGL(k_init_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
     else if (g.kind == 1) hipLaunchKernelGGL(k_init_z<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
     else hipLaunchKernelGGL(k_init_z<4>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
     AA_CHECK_LAUNCH();
@@ -2188,6 +2210,11 @@ void launch_aa_mix(Seg2 G, double* cur, long long eff, double* dF, double* dG, C
 
 void launch_test_prox(int op, const double* prm4, const double* in, int n, double* out, int* iters, hipStream_t s) {
     if (n <= 0) return;
+    if (op == 5) {
+        hipLaunchKernelGGL(k_test_hinge_prox, dim3(blocks_for(n)), dim3(kBlock), 0, s, prm4[0], in, n, out);
+        AA_CHECK_LAUNCH();
+        return;
+    }
     hipLaunchKernelGGL(k_test_prox, dim3((n + 63) / 64), dim3(64), 0, s, op, prm4[0], prm4[1], prm4[2], prm4[3], in, n, out,
                        iters);
     AA_CHECK_LAUNCH();

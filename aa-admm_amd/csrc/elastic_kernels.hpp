@@ -11,7 +11,7 @@ constexpr double kCombEps = 1e-20; // Solver.cpp:93 eps
 
 // One homogeneous block of energy terms (same kind / material / Lame), SoA on device.
 struct GroupDev {
-    int kind;            // 0 tet, 1 tri, 2 collision point (CollisionEnergyTerm.hpp:41-117)
+    int kind;            // 0 tet, 1 tri, 2 collision point (CollisionEnergyTerm.hpp:41-117), 3 bending hinge
     int mat;             // 0 linear, 1 NeoHookean, 2 StVK
     int count;           // elements
     int nv, ncol, dim;   // 4/3/9 for tets, 3/2/6 for tris
@@ -60,6 +60,13 @@ struct MeshCarryDev {
     const int* leaf_vid;     // [tris][3] vertex ids of leaf triangle k (MeshRefitTables::leaf_vid)
 };
 __host__ __device__ constexpr int ncol_of(int nv) { return nv > 1 ? nv - 1 : 1; }   // 1 vertex: identity reduction
+// The element kernels' shape parameter S: a vertex count (1, 3, 4: the simplex shapes, ncol_of(S)
+// columns), or 16 nv + ncol for a shape whose column count is its own. kShapeHinge: the bending
+// hinge (GroupDev::kind 3), four vertices and the one column z = K x; its rest length r[count]
+// rides in GroupDev::vol, which no kernel reads for this kind otherwise.
+constexpr int kShapeHinge = 16 * 4 + 1;
+__host__ __device__ constexpr int shape_nv(int s) { return s < 16 ? s : s / 16; }
+__host__ __device__ constexpr int shape_nc(int s) { return s < 16 ? ncol_of(s) : s % 16; }
 
 // Device-side control block: residual bookkeeping, reject/done flags, Anderson state.
 struct Ctrl {

@@ -127,6 +127,11 @@ class Scene:
     # new parameters or None for "leave as is"; step k runs against entry k - 1 and the last entry
     # holds on (capi.run_scene, with the poses)
     obstacle_motion: Optional[list] = None
+    # bending: a list of (tris (m, 3) int32, k_bend, flat_rest) -- hinges on the interior edges of each
+    # triangle list, rest shape from rest_x (capi.solver_from_scene binds them after the groups,
+    # Solver.add_bending). Not an ElementGroup: the reference has no bending term, so the oracle and the
+    # reference driver never see it. None = a pure membrane, today's scene.
+    bending: Optional[list] = None
 
     @property
     def rest_x(self) -> np.ndarray:
@@ -195,6 +200,23 @@ def tri_blocks(nx: int, ny: int):
     tris = np.stack([np.stack([d, a, e], 1), np.stack([a, b, e], 1),
                      np.stack([b, c, e], 1), np.stack([c, d, e], 1)], axis=1).reshape(-1, 3)
     return verts, tris.astype(np.int32)
+
+
+def tri_grid(nx: int, ny: int, size: float = 1.0):
+    """Vertices ((nx + 1)(ny + 1), 3) in the x-z plane, node j (nx + 1) + i at (i, 0, j) size / nx,
+    and triangles (2 nx ny, 3): every cell (a b / c d) cut into (a, b, d) and (a, d, c), consistently
+    oriented. 3 nx ny - nx - ny interior edges."""
+    xs = np.linspace(0.0, size, nx + 1)
+    zs = np.linspace(0.0, size * ny / nx, ny + 1)
+    verts = np.array([[x, 0.0, z] for z in zs for x in xs], np.float64)
+    tris = []
+    for j in range(ny):
+        for i in range(nx):
+            a = j * (nx + 1) + i
+            b, c = a + 1, a + nx + 1
+            d = c + 1
+            tris += [[a, b, d], [a, d, c]]
+    return verts, np.array(tris, np.int32)
 
 
 def tet_blocks(cx: int, cy: int, cz: int):
@@ -270,8 +292,10 @@ def tet_masses(verts, tets, density=1522.0):
 # ----------------------------------------------------------------------------------------
 
 def cloth(nx: int = 112, ny: int = 112, size: float = 2.0, *, variant=VARIANT_H, aa_m=6, iters=100,
-          n_steps=1, accel=1) -> Scene:
+          n_steps=1, accel=1, bend=None) -> Scene:
     """C2: cloth drop (`make_tri_blocks(112,112)` scaled to `size` m, 50 176 tris).
+    bend: a bending stiffness k_bend for hinges on the sheet's interior edges (flat rest); None = the
+    reference's pure membrane.
 
     Material Lame(50, 0.1) with strain limits [0.95, 1.05] and area density 1 as the
     windyflag sample (windyflag.cpp:84-87, AddMeshes.hpp:203); two corners of the min-x
@@ -287,7 +311,29 @@ def cloth(nx: int = 112, ny: int = 112, size: float = 2.0, *, variant=VARIANT_H,
     pins = np.array([up, down], dtype=np.int32)
     return Scene(x=v, masses=m, groups=[ElementGroup(TRI, LINEAR, 50.0, 0.1, t, 0.95, 1.05)],
                  pin_idx=pins, pin_pts=v[pins].copy(), pin_vel=np.zeros((2, 3)), variant=variant,
-                 iters=iters, aa_m=aa_m, n_steps=n_steps, accel=accel, name=f"cloth{nx}x{ny}")
+                 iters=iters, aa_m=aa_m, n_steps=n_steps, accel=accel, name=f"cloth{nx}x{ny}",
+                 bending=None if bend is None else [(t, float(bend), True)])
+
+
+def cantilever_strip(nx=12, ny=12, k_bend=1e-2, *, flat_rest=True, size=0.1, clamp=True, membrane=True, iters=30, aa_m=6,
+                     accel=1, n_steps=10, penalty=1.0) -> Scene:
+    """Demo of the bending term: a tri_grid(nx, ny) strip of length `size` lying in the x-z plane
+    under gravity, held at its x = 0 edge; cloth()'s membrane (Lame(50, 0.1), strain limits
+    [0.95, 1.05], area density 1) plus hinges of stiffness k_bend on its interior edges ((u,x)
+    variant). clamp: the next column of nodes is pinned too, which fixes the strip's slope at the
+    edge -- a cantilever. Pinning the edge alone leaves a free hinge line: no hinge spans a boundary
+    edge, so the strip turns about it at no cost (and, stiff, its tip falls faster than a limp
+    strip's, as a rod's does). size: a strip of length L sags under its own weight once L^3 exceeds
+    about k_bend / (density g), i.e. L = 0.05 for k_bend 1e-3 and 0.2 for 1e-1; the default 0.1 lies
+    between, so that range of k_bend spans limp to stiff. k_bend None = no bending. membrane False =
+    hinges only."""
+    v, t = tri_grid(nx, ny, size)
+    pins = np.nonzero(v[:, 0] <= (1.5 if clamp else 0.5) * size / nx)[0].astype(np.int32)
+    return Scene(x=v, masses=tri_masses(v, t, 1.0),
+                 groups=[ElementGroup(TRI, LINEAR, 50.0, 0.1, t, 0.95, 1.05)] if membrane else [],
+                 pin_idx=pins, pin_pts=v[pins].copy(), pin_vel=np.zeros((len(pins), 3)), variant=VARIANT_H,
+                 iters=iters, aa_m=aa_m, n_steps=n_steps, accel=accel, penalty=penalty, name=f"cantilever_strip{nx}x{ny}",
+                 bending=None if k_bend is None else [(t, float(k_bend), bool(flat_rest))])
 
 
 def cantilever(cx=20, cy=4, cz=5, material=NEOHOOKEAN, *, variant=VARIANT_X, aa_m=6, iters=50,
@@ -554,11 +600,11 @@ def torus_mesh(nu=16, nv=8, R=1.0, r=0.4, center=(0.0, 0.0, 0.0)):
     return V, np.asarray(F, np.int32)
 
 
-def cloth_on_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15, ring=0.3) -> Scene:
+def cloth_on_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15, ring=0.3, bend=None) -> Scene:
     """Demo of the mesh obstacle: an unpinned cloth sheet dropped flat onto a torus lying in the
     x-z plane ((u,x) variant; every node collision-checked). The torus' major radius is `ring` times
-    the sheet's side, its tube radius 0.4 of that."""
-    sc = cloth(nx, ny, variant=VARIANT_H, aa_m=aa_m, iters=iters, n_steps=n_steps, accel=accel)
+    the sheet's side, its tube radius 0.4 of that. bend: cloth()'s."""
+    sc = cloth(nx, ny, variant=VARIANT_H, aa_m=aa_m, iters=iters, n_steps=n_steps, accel=accel, bend=bend)
     sc.name = "cloth_on_torus"
     x = np.array(sc.x, np.float64)
     ext = x.max(0) - x.min(0)
@@ -586,11 +632,11 @@ def rotation_y(angle: float) -> np.ndarray:
 
 
 def cloth_on_spinning_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15, dtheta=0.05,
-                            friction=None) -> Scene:
+                            friction=None, bend=None) -> Scene:
     """Demo of the kinematic mesh obstacle: cloth_on_torus with the torus turning about the y axis
     by `dtheta` per step (step k runs against the torus turned by k dtheta). friction: the torus'
     Coulomb coefficient -- with it the cloth is carried round; None = no friction pass."""
-    sc = cloth_on_torus(nx, ny, iters=iters, aa_m=aa_m, accel=accel, n_steps=n_steps, drop=drop)
+    sc = cloth_on_torus(nx, ny, iters=iters, aa_m=aa_m, accel=accel, n_steps=n_steps, drop=drop, bend=bend)
     sc.name = "cloth_on_spinning_torus"
     poses = np.zeros((n_steps, 1, 12))
     for k in range(n_steps):
@@ -602,12 +648,12 @@ def cloth_on_spinning_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=
 
 
 def cloth_on_breathing_torus(nx=12, ny=12, *, iters=30, aa_m=6, accel=1, n_steps=10, drop=0.15, amplitude=0.25,
-                             period=20, ring=0.42) -> Scene:
+                             period=20, ring=0.42, bend=None) -> Scene:
     """Demo of the deforming mesh obstacle: cloth_on_torus -- with a ring wide enough that the middle
     of the sheet's edges comes to lie on the tube while the corners hang free -- and the torus' tube
     radius oscillating, r_k = r (1 + amplitude sin^2(pi k / period)) in step k: never below the
     radius r the torus is added with, and at its largest in steps period / 2, 3 period / 2, ..."""
-    sc = cloth_on_torus(nx, ny, iters=iters, aa_m=aa_m, accel=accel, n_steps=n_steps, drop=drop, ring=ring)
+    sc = cloth_on_torus(nx, ny, iters=iters, aa_m=aa_m, accel=accel, n_steps=n_steps, drop=drop, ring=ring, bend=bend)
     sc.name = "cloth_on_breathing_torus"
     R = ring * float(max(sc.x.max(0) - sc.x.min(0)))
     r = 0.4 * R
@@ -639,7 +685,7 @@ def kuhn_tet_blocks(cx: int, cy: int, cz: int):
 
 
 def cloth_on_soft_block(nx=12, ny=12, *, cells=(3, 2, 3), cell=0.3, E=5e4, nu=0.3, iters=30, aa_m=6, accel=1, n_steps=8,
-                        drop=0.05) -> Scene:
+                        drop=0.05, bend=None) -> Scene:
     """Demo of the bound mesh obstacle (body-to-body contact, (u,x) variant): a linear-tet block of
     `cells` cubes of side `cell` (kuhn_tet_blocks: conforming, so its boundary is closed), its bottom-face nodes pinned, soft enough to sag under its own
     weight over the steps; its boundary faces are mesh obstacle 0, bound to its surface nodes, so
@@ -668,6 +714,8 @@ def cloth_on_soft_block(nx=12, ny=12, *, cells=(3, 2, 3), cell=0.3, E=5e4, nu=0.
                groups=[ElementGroup(TET, LINEAR, E, nu, bt), ElementGroup(TRI, LINEAR, 50.0, 0.1, (ct + nb).astype(np.int32), 0.95, 1.05)],
                pin_idx=pins, pin_pts=bv[pins].copy(), pin_vel=np.zeros((len(pins), 3)), variant=VARIANT_H, iters=iters,
                aa_m=aa_m, n_steps=n_steps, accel=accel, name="cloth_on_soft_block", rest=rest)
+    if bend is not None:   # hinges on the cloth sheet (rest shape: the flat sheet in `rest`)
+        sc.bending = [((ct + nb).astype(np.int32), float(bend), True)]
     sc.mesh_obstacles = [(bv[surf].copy(), local[faces].astype(np.int32))]
     sc.mesh_obstacle_bindings = [surf]
     sc.collision_idx = np.arange(nb, nb + len(cx), dtype=np.int32)

@@ -114,6 +114,23 @@ int aa_elastic_add_tets_var(aa_elastic h, const double* verts3, const int* tets4
                             const aa_lame* lame_per_tet /* [n_tets] */, int vertex_offset);
 int aa_elastic_add_tris_var(aa_elastic h, const double* verts3, const int* tris3, int n_tris,
                             const aa_lame* lame_per_tri /* [n_tris] */, int vertex_offset);
+/* Bending (no counterpart in the reference, whose cloth is a pure membrane): one hinge per interior
+ * edge of the triangle list, i.e. an edge shared by exactly two triangles; boundary edges make none.
+ * Hinge vertices (x0, x1, x2, x3): x0 < x1 the edge's endpoints, x2 the opposite vertex in the
+ * triangle with the lower index, x3 the other. With cot(p; a, b) = ((a-p).(b-p)) / |(a-p)x(b-p)| on
+ * the rest positions, a0 = cot(x0; x1, x2), a1 = cot(x1; x0, x2), b0 = cot(x0; x1, x3), b1 =
+ * cot(x1; x0, x3), the reduction row is K = (a1 + b1, a0 + b0, -(a0 + a1), -(b0 + b1)) and z = K x in
+ * R^3. Energy 1/2 kappa (|z| - r)^2, kappa = 3 k_bend / (sum of the two rest areas); flat_rest != 0:
+ * r = 0 (the quadratic isometric bending model of Bergou et al. 2006), else r = |K xbar| of the rest
+ * shape, so that a curved rest shape is an equilibrium. ADMM weight sqrt(kappa). Rest shape from
+ * verts3[tris3], node ids tris3 + vertex_offset; *n_hinges (optional) receives the hinge count, 0 for
+ * a list without an interior edge. Before initialize only (AA_ERR_STATE after). AA_ERR_ARG naming the
+ * first offending element: an index out of range, a non-finite vertex, k_bend not finite or not > 0,
+ * an edge in more than two triangles, two triangles running along their shared edge in the same
+ * direction; AA_ERR_NUMERIC: a zero-area triangle. initialize refuses a solver with hinges in
+ * AA_VARIANT_Z and one partitioned over more than one rank. */
+int aa_elastic_add_bending(aa_elastic h, const double* verts3, const int* tris3, int n_tris, double k_bend,
+                           int flat_rest, int vertex_offset, int* n_hinges);
 /* Solver::set_pins(inds, points): points3 == NULL pins in place (Solver.cpp:280-315). */
 int aa_elastic_set_pins(aa_elastic h, const int* inds, const double* points3, int n_pins);
 
@@ -546,7 +563,8 @@ int aa_geom_set_comm(aa_geom h, aa_comm c);
  *   aa_test_prox: op 0 TetEnergyTerm::prox (in/out 9 per tet, TetEnergyTerm.cpp:74-96),
  *     1 NeoHookeanTet / 2 StVKTet prox (L-BFGS, TetEnergyTerm.cpp:151-162; prm4 = E, nu, h with
  *     vol = h^3/6; iters = L-BFGS iterations, -1 on a line-search failure), 3 / 4 TriEnergyTerm
- *     prox of the H / X solver copy (6 per tri; prm4[2..3] = limit_min, limit_max)
+ *     prox of the H / X solver copy (6 per tri; prm4[2..3] = limit_min, limit_max), 5 the bending
+ *     hinge's prox (3 per hinge; prm4[0] = r)
  *   aa_test_cod_solve: the Anderson normal-equation solve (Eigen CompleteOrthogonalDecomposition,
  *     AndersonAcceleration.h:186-188) of a k x k column-major M
  *   aa_test_geom_project: Constraint::project_impl of plane (k 3..8) / angle (k 3) / edge (k 2)

@@ -58,7 +58,7 @@ public:
 class EnergyTerm {
 public:
     virtual ~EnergyTerm() {}
-    int kind = 0, material = AA_LINEAR;   // kind 0 tet, 1 tri
+    int kind = 0, material = AA_LINEAR;   // kind 0 tet, 1 tri, 3 bending hinges (BendingEnergyTerm)
     Lame lame;
     std::vector<Lame> lames;     // per-element materials ([count]); empty: `lame` for every element
     std::vector<double> verts;   // rest shape (as given to create_*_from_mesh)
@@ -120,6 +120,29 @@ inline void create_tris_from_mesh(std::vector<std::shared_ptr<EnergyTerm>>& ener
     if ((int)lames.size() != n_tris) throw std::runtime_error("create_tris_from_mesh: one Lame per triangle expected");
     create_tris_from_mesh<IN_SCALAR, TYPE>(energyterms, verts, inds, n_tris, Lame(), vertex_offset);
     energyterms.back()->lames = lames;
+}
+
+// Bending (aa_elastic_add_bending; the reference has no such term): hinges on the interior edges of
+// a triangle list, stiffness k_bend; flat_rest false keeps the rest shape's curvature as the equilibrium.
+class BendingEnergyTerm : public EnergyTerm {
+public:
+    double k_bend = 0;
+    bool flat_rest = true;
+};
+template <typename IN_SCALAR>
+inline void create_bending_from_mesh(std::vector<std::shared_ptr<EnergyTerm>>& energyterms, const IN_SCALAR* verts,
+                                     const int* inds, int n_tris, double k_bend, bool flat_rest, const int vertex_offset) {
+    auto e = std::make_shared<BendingEnergyTerm>();
+    e->kind = 3;
+    e->k_bend = k_bend;
+    e->flat_rest = flat_rest;
+    int nv = 0;
+    for (int i = 0; i < 3 * n_tris; ++i) nv = std::max(nv, inds[i] + 1);
+    e->verts.assign(verts, verts + 3 * (size_t)nv);
+    e->inds.assign(inds, inds + 3 * (size_t)n_tris);
+    e->count = n_tris;
+    e->vertex_offset = vertex_offset;
+    energyterms.push_back(e);
 }
 
 typedef std::array<double, 3> Vec3d;
@@ -414,7 +437,10 @@ public:
             for (auto& e : energyterms) {
                 aa_lame l = e->lame.c();
                 int rc;
-                if (!e->lames.empty()) {   // per-element materials: the _var calls
+                if (const BendingEnergyTerm* b = dynamic_cast<const BendingEnergyTerm*>(e.get())) {
+                    rc = aa_elastic_add_bending(h_, b->verts.data(), b->inds.data(), b->count, b->k_bend, b->flat_rest ? 1 : 0,
+                                                b->vertex_offset, nullptr);
+                } else if (!e->lames.empty()) {   // per-element materials: the _var calls
                     std::vector<aa_lame> ls;
                     for (auto& le : e->lames) ls.push_back(le.c());
                     rc = e->kind == 0
