@@ -17,13 +17,14 @@ LIB_PATH = os.environ.get("AA_ADMM_LIB") or os.path.join(HERE, "libaa_admm.so") 
 
 AA_LINEAR, AA_NEOHOOKEAN, AA_STVK = 0, 1, 2
 AA_VARIANT_Z, AA_VARIANT_UX = 0, 1
+AA_SPRING, AA_SPRING_TETHER, AA_SPRING_STRUT, AA_SPRING_HARD = 0, 1, 2, 4
 NOACC, ANDERSON = 0, 1
 
 EXPORTS = [
     "aa_last_error", "aa_version", "aa_ctx_create", "aa_ctx_destroy", "aa_ctx_synchronize", "aa_ctx_bench_read",
     "aa_ctx_warm_dense", "aa_lame_from_young",
     "aa_settings_default", "aa_elastic_create", "aa_elastic_destroy", "aa_elastic_add_nodes", "aa_elastic_add_tets",
-    "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_add_bending", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
+    "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_add_bending", "aa_elastic_add_springs", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
     "aa_elastic_add_obstacle", "aa_elastic_add_mesh_obstacle", "aa_elastic_set_mesh_obstacle_pose",
     "aa_elastic_get_mesh_obstacle_pose", "aa_elastic_set_mesh_obstacle_vertices", "aa_elastic_get_mesh_obstacle_vertices",
     "aa_elastic_bind_mesh_obstacle", "aa_elastic_mesh_obstacle_status", "aa_elastic_set_mesh_obstacle_exempt",
@@ -348,6 +349,21 @@ class Solver:
                                           C.c_int(1 if flat_rest else 0), C.c_int(vertex_offset), C.byref(k)))
         return k.value
 
+    def add_springs(self, pairs, k, rest=None, mode=AA_SPRING, verts=None, vertex_offset=0):
+        """Two-node springs (aa_elastic_add_springs): pairs (n, 2), stiffness k (a scalar is broadcast),
+        rest lengths rest (n,) or None = the pairs' distances in verts (default: the solver's current
+        node positions). mode: AA_SPRING / AA_SPRING_TETHER / AA_SPRING_STRUT, | AA_SPRING_HARD.
+        Before initialize."""
+        p = np.ascontiguousarray(pairs, np.int32).reshape(-1)
+        n = len(p) // 2
+        kk = np.ascontiguousarray(np.broadcast_to(np.asarray(k, np.float64), (n,)))
+        r = None if rest is None else np.ascontiguousarray(np.broadcast_to(np.asarray(rest, np.float64), (n,)))
+        if verts is None and rest is None:
+            verts = self.x
+        v = None if verts is None else np.ascontiguousarray(verts, np.float64).reshape(-1)
+        _chk(lib().aa_elastic_add_springs(self.h, None if v is None else _dp(v), _ip(p), C.c_int(n), C.c_int(int(mode)), _dp(kk),
+                                          None if r is None else _dp(r), C.c_int(vertex_offset)))
+
     def set_pins(self, inds, points=None):
         i = np.ascontiguousarray(inds, np.int32).reshape(-1)
         if points is None:
@@ -665,6 +681,8 @@ def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
             s.add_tris(scene.rest_x, g.idx, lame)
     for tris, k_bend, flat_rest in getattr(scene, "bending", None) or []:   # after the groups
         s.add_bending(scene.rest_x, tris, k_bend, flat_rest)
+    for pairs, k, rest, mode in getattr(scene, "springs", None) or []:   # after the bending entries
+        s.add_springs(pairs, k, rest, mode, verts=scene.rest_x)
     s.set_pins(scene.pin_idx, scene.pin_pts)
     for kind, prm in getattr(scene, "obstacles", []):
         s.add_obstacle(kind, prm)
@@ -946,7 +964,7 @@ def run_geom(ctx: Context, sc, comm=None):
 
 def hook_prox(ctx: Context, op, prm4, X):
     """op 0 linear tet, 1 NeoHookean, 2 StVK (prm4 = E, nu, h), 3 / 4 tri H / X prox (prm4[2:] =
-    limits), 5 the bending hinge's prox (prm4[0] = r); X (n, 9|6|3). Returns (out, L-BFGS iterations)."""
+    limits), 5 the bending hinge's prox (prm4[0] = r), 6 the spring's prox (prm4 = L, mode); X (n, 9|6|3). Returns (out, L-BFGS iterations)."""
     X = np.ascontiguousarray(X, np.float64)
     n = X.shape[0]
     out, it = np.zeros_like(X), np.zeros(n, np.int32)

@@ -189,6 +189,14 @@ int aa_elastic_add_bending(aa_elastic h, const double* verts3, const int* tris3,
     });
 }
 
+int aa_elastic_add_springs(aa_elastic h, const double* verts3, const int* pairs2, int n_springs, int mode, const double* k,
+                           const double* rest, int vertex_offset) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        h->s->add_springs(verts3, pairs2, n_springs, mode, k, rest, vertex_offset);
+    });
+}
+
 int aa_elastic_set_pins(aa_elastic h, const int* inds, const double* pts3, int n) {
     return guarded([&] { NEED(h, "null handle"); h->s->set_pins(inds, pts3, n); });
 }
@@ -668,12 +676,12 @@ int with_device_arrays(aa_ctx ctx, F&& f) {
 
 extern "C" int aa_test_prox(aa_ctx ctx, int op, const double* prm4, const double* in, int n, double* out, int* iters) {
     return with_device_arrays(ctx, [&](hipStream_t s) {
-        NEED(prm4 && in && out && n >= 0 && op >= 0 && op <= 5, "aa_test_prox: bad argument");
-        const int D = op == 5 ? 3 : op >= 3 ? 6 : 9;
+        NEED(prm4 && in && out && n >= 0 && op >= 0 && op <= 6, "aa_test_prox: bad argument");
+        const int D = op >= 5 ? 3 : op >= 3 ? 6 : 9;
         aa::DevBuf<double> di, dout((size_t)D * std::max(n, 1));
         aa::DevBuf<int> dit(std::max(n, 1));
         di.upload(in, (size_t)D * n, s);
-        if (op == 5) AA_HIP(hipMemsetAsync(dit.p, 0, sizeof(int) * std::max(n, 1), s));   // closed form: no iterations
+        if (op >= 5) AA_HIP(hipMemsetAsync(dit.p, 0, sizeof(int) * std::max(n, 1), s));   // closed form: no iterations
         aa::launch_test_prox(op, prm4, di.p, n, dout.p, dit.p, s);
         AA_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * D * n, hipMemcpyDeviceToHost, s));
         if (iters) AA_HIP(hipMemcpyAsync(iters, dit.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));

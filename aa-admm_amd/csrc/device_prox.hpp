@@ -37,6 +37,25 @@ __device__ __forceinline__ void hinge_prox(const double* v, double r, double* ou
     out[0] = s * v[0]; out[1] = s * v[1]; out[2] = s * v[2];
 }
 
+// ------------------------------------------------------------------ springs (3x1, two nodes)
+// z = x_b - x_a, rest length L, w^2 = k (springs.hpp). mode & 3: 0 two-sided, U = 1/2 k (|z| - L)^2,
+// the hinge's statement s = 1/2 + 1/2 (L / n); 1 tether, U = 1/2 k max(0, |z| - L)^2: slack at
+// n <= L, z = v bitwise; 2 strut, U = 1/2 k max(0, L - |z|)^2: slack at n >= L. mode & 4 (hard): U
+// the indicator of |z| = L / <= L / >= L, s = L / n where the soft form would act. n = 0 has no
+// direction: z = v in every mode (stated, not derived).
+__device__ __forceinline__ void spring_prox(const double* v, double L, int mode, double* out) {
+    const double n = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    const int side = mode & 3;
+    const bool slack = n == 0.0 || (side == 1 && n <= L) || (side == 2 && n >= L);
+    if (slack) {
+        out[0] = v[0]; out[1] = v[1]; out[2] = v[2];
+        return;
+    }
+    const double q = L / n;
+    const double s = (mode & 4) ? q : 0.5 + 0.5 * q;
+    out[0] = s * v[0]; out[1] = s * v[1]; out[2] = s * v[2];
+}
+
 // ------------------------------------------------------------------ triangles (3x2)
 // z: column-major 3x2 (z[c*3+r]); mode 1 = UX (hard_zxu), 0 = Z (xzu)
 __device__ __forceinline__ void tri_prox(const double* z, double* out, int mode, double lmin, double lmax) {

@@ -16,6 +16,7 @@
 #include "elastic_kernels.hpp"
 #include "mesh_obstacle.hpp"
 #include "mesh_refit.hpp"
+#include "springs.hpp"
 
 namespace aa {
 
@@ -75,6 +76,9 @@ public:
                       int vertex_offset, const aa_lame* per_element = nullptr);
     // bending hinges on the interior edges of a triangle list (bending.hpp); returns their count
     int add_bending(const double* verts3, const int* tris3, int n_tris, double k_bend, bool flat_rest, int vertex_offset);
+    // two-node springs (springs.hpp): one group of kind 4 per call; node ids pairs2 + vertex_offset
+    void add_springs(const double* verts3, const int* pairs2, int n_springs, int mode, const double* k, const double* rest,
+                     int vertex_offset);
     void set_pins(const int* inds, const double* pts3, int n);
     // energy-based collisions of the (u,x) variant (admm_anderson_hard_zxu Solver.cpp:318-348)
     void add_obstacle(int type, const double* params);
@@ -154,7 +158,7 @@ public:
 
 private:
     struct HostGroup {
-        int kind, material, nv, ncol;   // kind 3 (bending hinge): G holds K, vol the rest length r
+        int kind, material, nv, ncol;   // kind 3 (bending hinge): G holds K, vol the rest length r; kind 4 (spring): G = (-1, +1), vol = L, material = the mode
         aa_lame lame;
         std::vector<int> idx;       // [count][nv] global node ids
         std::vector<double> G;      // [count][ncol][nv]

@@ -246,8 +246,8 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
         double F[D], Cp[D], uu[D], vin[D], zz[D];
         gather_F<S>(g, e, xfull, nf, F, Cp);
         const double w = g.w[e];
-        double rest = 0.0;   // the hinge's r, with the other loads
-        if constexpr (S == kShapeHinge) rest = g.vol[e];
+        double rest = 0.0;   // the hinge's r / the spring's L, with the other loads
+        if constexpr (S == kShapeHinge || S == kShapeSpring) rest = g.vol[e];
         load_u<D>(g, e, u, uu);
 #pragma unroll
         for (int i = 0; i < D; ++i) vin[i] = F[i] + uu[i] / w;
@@ -263,6 +263,8 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
             else dev::tri_prox(vin, zz, variant, g.lmin, g.lmax);
         } else if constexpr (S == kShapeHinge) {
             dev::hinge_prox(vin, rest, zz);
+        } else if constexpr (S == kShapeSpring) {
+            dev::spring_prox(vin, rest, g.mat, zz);
         } else if constexpr (HYPER == 0) {
             dev::tet_linear_prox(vin, zz);
         } else {
@@ -817,8 +819,8 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
                                                     V... gvp) {
     constexpr bool VAR = kVar<V...>;
     if (gated(ctrl, redo)) return;
-    // (a hinge counts as a shape of its own below: NV is 0 for it, none of the simplex branches)
-    constexpr int NV = S == kShapeHinge ? 0 : shape_nv(S), D = 3 * shape_nc(S);
+    // (a hinge or a spring counts as a shape of its own below: NV is 0 for it, none of the simplex branches)
+    constexpr int NV = S == kShapeHinge || S == kShapeSpring ? 0 : shape_nv(S), D = 3 * shape_nc(S);
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= g.count) return;
     // the gradient (mode 1) needs only z: it runs before the element's gathers, so its
@@ -840,9 +842,9 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
     }
     if (mode == 1) {
         double gr[D];
-        if constexpr (NV == 3 || NV == 1 || S == kShapeHinge) {
+        if constexpr (NV == 3 || NV == 1 || S == kShapeHinge || S == kShapeSpring) {
             // TriEnergyTerm::get_gradient / Collision::get_gradient throw in the reference; a hinge
-            // group is refused in the Z variant (initialize), so mode 1 never reaches it
+            // or spring group is refused in the Z variant (initialize), so mode 1 never reaches it
             if (ctrl) ctrl->fail = 2;
 #pragma unroll
             for (int i = 0; i < D; ++i) gr[i] = 0;
@@ -1780,6 +1782,17 @@ __global__ __launch_bounds__(kBlock) void k_test_hinge_prox(double r, const doub
     for (int i = 0; i < 3; ++i) out[3 * (size_t)e + i] = z[i];
 }
 
+// op 6: the spring prox (3 in / out per spring, prm = L, mode)
+__global__ __launch_bounds__(kBlock) void k_test_spring_prox(double L, int mode, const double* __restrict__ in, int n,
+                                                             double* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const double v[3] = {in[3 * (size_t)e], in[3 * (size_t)e + 1], in[3 * (size_t)e + 2]};
+    double z[3];
+    dev::spring_prox(v, L, mode, z);
+    for (int i = 0; i < 3; ++i) out[3 * (size_t)e + i] = z[i];
+}
+
 // aa_test_mesh_sdf: the production mesh_signed_distance decides `inside` (root-box cull included);
 // a query it turns away is walked all the same for the report (c, +|q - c|, triangle)
 __global__ __launch_bounds__(kBlock) void k_test_mesh_sdf(const MeshObsDev* __restrict__ mesh, const double* __restrict__ q,
@@ -1906,7 +1919,8 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
         AA_CHECK_LAUNCH();
         return;
     }
-    if (g.kind == 3) hipLaunchKernelGGL((k_local_z<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+    if (g.kind == 4) hipLaunchKernelGGL((k_local_z<kShapeSpring, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+    else if (g.kind == 3) hipLaunchKernelGGL((k_local_z<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
     else if (g.kind == 2 && meshes) hipLaunchKernelGGL((k_local_z<1, 0, const MeshObsDev*>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, meshes);
     else if (g.kind == 2) hipLaunchKernelGGL((k_local_z<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
     else if (g.kind == 1 && var) hipLaunchKernelGGL((k_local_z<3, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, var);
@@ -1945,7 +1959,8 @@ void launch_resid_update_u(const GroupDev& g, const double* xfull, const double*
                            int nf, Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 3) hipLaunchKernelGGL(k_resid_u<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+    if (g.kind == 4) hipLaunchKernelGGL(k_resid_u<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+    else if (g.kind == 3) hipLaunchKernelGGL(k_resid_u<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
     else if (g.kind == 2) hipLaunchKernelGGL(k_resid_u<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
     else if (g.kind == 1) hipLaunchKernelGGL(k_resid_u<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
     else hipLaunchKernelGGL(k_resid_u<4>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
@@ -1956,7 +1971,8 @@ void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, con
                     int nf, int mode, int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 3) hipLaunchKernelGGL((k_u_and_y<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+    if (g.kind == 4) hipLaunchKernelGGL((k_u_and_y<kShapeSpring, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+    else if (g.kind == 3) hipLaunchKernelGGL((k_u_and_y<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
     else if (g.kind == 2) hipLaunchKernelGGL((k_u_and_y<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
     else if (g.kind == 1) hipLaunchKernelGGL((k_u_and_y<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);   // no material reads
     else if (g.mat == 0 && var) hipLaunchKernelGGL((k_u_and_y<4, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl, var);
@@ -1970,7 +1986,8 @@ void launch_prim_z(const GroupDev& g, const double* xfull, const double* z, cons
                    Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 3) hipLaunchKernelGGL(k_prim_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+    if (g.kind == 4) hipLaunchKernelGGL(k_prim_z<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+    else if (g.kind == 3) hipLaunchKernelGGL(k_prim_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
     else if (g.kind == 2) hipLaunchKernelGGL(k_prim_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
     else if (g.kind == 1) hipLaunchKernelGGL(k_prim_z<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
     else hipLaunchKernelGGL(k_prim_z<4>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
@@ -1980,7 +1997,8 @@ void launch_prim_z(const GroupDev& g, const double* xfull, const double* z, cons
 void launch_init_z(const GroupDev& g, const double* xfull, double* z, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 3) hipLaunchKernelGGL(k_init_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+    if (g.kind == 4) hipLaunchKernelGGL(k_init_z<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+    else if (g.kind == 3) hipLaunchKernelGGL(k_init_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
     else if (g.kind == 2) hipLaunchKernelGGL(k_init_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
     else if (g.kind == 1) hipLaunchKernelGGL(k_init_z<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
     else hipLaunchKernelGGL(k_init_z<4>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
@@ -2212,6 +2230,11 @@ void launch_test_prox(int op, const double* prm4, const double* in, int n, doubl
     if (n <= 0) return;
     if (op == 5) {
         hipLaunchKernelGGL(k_test_hinge_prox, dim3(blocks_for(n)), dim3(kBlock), 0, s, prm4[0], in, n, out);
+        AA_CHECK_LAUNCH();
+        return;
+    }
+    if (op == 6) {
+        hipLaunchKernelGGL(k_test_spring_prox, dim3(blocks_for(n)), dim3(kBlock), 0, s, prm4[0], (int)prm4[1], in, n, out);
         AA_CHECK_LAUNCH();
         return;
     }

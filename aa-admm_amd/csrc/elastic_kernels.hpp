@@ -11,8 +11,8 @@ constexpr double kCombEps = 1e-20; // Solver.cpp:93 eps
 
 // One homogeneous block of energy terms (same kind / material / Lame), SoA on device.
 struct GroupDev {
-    int kind;            // 0 tet, 1 tri, 2 collision point (CollisionEnergyTerm.hpp:41-117), 3 bending hinge
-    int mat;             // 0 linear, 1 NeoHookean, 2 StVK
+    int kind;            // 0 tet, 1 tri, 2 collision point (CollisionEnergyTerm.hpp:41-117), 3 bending hinge, 4 spring
+    int mat;             // 0 linear, 1 NeoHookean, 2 StVK; kind 4: the spring mode (AA_SPRING_*)
     int count;           // elements
     int nv, ncol, dim;   // 4/3/9 for tets, 3/2/6 for tris
     int pinned;          // some element of the group has a pinned node (C_fix terms exist)
@@ -65,6 +65,9 @@ __host__ __device__ constexpr int ncol_of(int nv) { return nv > 1 ? nv - 1 : 1; 
 // hinge (GroupDev::kind 3), four vertices and the one column z = K x; its rest length r[count]
 // rides in GroupDev::vol, which no kernel reads for this kind otherwise.
 constexpr int kShapeHinge = 16 * 4 + 1;
+// kShapeSpring: the two-node spring (GroupDev::kind 4), row (-1, +1), the one column z = x_b - x_a;
+// its rest length L[count] rides in GroupDev::vol like the hinge's r, its mode in GroupDev::mat.
+constexpr int kShapeSpring = 16 * 2 + 1;
 __host__ __device__ constexpr int shape_nv(int s) { return s < 16 ? s : s / 16; }
 __host__ __device__ constexpr int shape_nc(int s) { return s < 16 ? ncol_of(s) : s % 16; }
 

@@ -35,6 +35,8 @@ TET, TRI = 0, 1
 OBS_FLOOR, OBS_SLIDE_FLOOR, OBS_SPHERE, OBS_PLANE_HALF_SPHERE, OBS_CYLINDER = 0, 1, 2, 3, 4
 OBS_MESH = 5   # PassiveMesh (:138-178): Scene.mesh_obstacles / capi.Solver.add_mesh_obstacle
 LINEAR, NEOHOOKEAN, STVK = 0, 1, 2
+# spring modes (include/aa_admm.h AA_SPRING_*): two-sided, slack below / above L; | SPRING_HARD
+SPRING, SPRING_TETHER, SPRING_STRUT, SPRING_HARD = 0, 1, 2, 4
 VARIANT_X, VARIANT_H = 0, 1  # admm_anderson_xzu (z-AA) / admm_anderson_hard_zxu ((u,x)-AA)
 
 
@@ -132,6 +134,11 @@ class Scene:
     # Solver.add_bending). Not an ElementGroup: the reference has no bending term, so the oracle and the
     # reference driver never see it. None = a pure membrane, today's scene.
     bending: Optional[list] = None
+    # springs: a list of (pairs (m, 2) int32, k (scalar or (m,)), rest ((m,), scalar or None = the
+    # pairs' distances in rest_x), mode) -- two-node springs, tethers and struts, one group per entry
+    # (capi.solver_from_scene binds them after the bending entries, Solver.add_springs). Like
+    # bending, unknown to the oracle and the reference driver. None = no springs, today's scene.
+    springs: Optional[list] = None
 
     @property
     def rest_x(self) -> np.ndarray:
@@ -334,6 +341,125 @@ def cantilever_strip(nx=12, ny=12, k_bend=1e-2, *, flat_rest=True, size=0.1, cla
                  pin_idx=pins, pin_pts=v[pins].copy(), pin_vel=np.zeros((len(pins), 3)), variant=VARIANT_H,
                  iters=iters, aa_m=aa_m, n_steps=n_steps, accel=accel, penalty=penalty, name=f"cantilever_strip{nx}x{ny}",
                  bending=None if k_bend is None else [(t, float(k_bend), bool(flat_rest))])
+
+
+# ----------------------------------------------------------------------------------------
+# springs, tethers and struts (Scene.springs)
+# ----------------------------------------------------------------------------------------
+
+def pair_lengths(x, pairs):
+    """|x[b] - x[a]| per pair, summed as the host builder does."""
+    d = np.asarray(x, np.float64)[np.asarray(pairs)[:, 1]] - np.asarray(x, np.float64)[np.asarray(pairs)[:, 0]]
+    return np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+
+
+def net_pairs(nx: int, ny: int, shear=True):
+    """Pairs (m, 2) int32 of an nx x ny grid of nodes, node j nx + i: the structural springs along
+    the rows, then along the columns, then (shear) both diagonals of every cell."""
+    node = lambda i, j: j * nx + i
+    p = [(node(i, j), node(i + 1, j)) for j in range(ny) for i in range(nx - 1)]
+    p += [(node(i, j), node(i, j + 1)) for j in range(ny - 1) for i in range(nx)]
+    if shear:
+        for j in range(ny - 1):
+            for i in range(nx - 1):
+                p += [(node(i, j), node(i + 1, j + 1)), (node(i + 1, j), node(i, j + 1))]
+    return np.array(p, np.int32).reshape(-1, 2)
+
+
+def spring_net(nx=5, ny=5, *, k=50.0, size=1.0, node_mass=0.01, mode=SPRING, rest_scale=None, shear=True, gravity=-9.8,
+               iters=30, aa_m=6, accel=1, n_steps=5, penalty=1.0) -> Scene:
+    """Demo of the spring term: a net of nx x ny nodes in the x-z plane, `size` wide, made of springs
+    alone -- structural ones along the grid lines plus shear ones on the cells' diagonals, stiffness
+    k -- its four corners pinned, under gravity ((u,x) variant). Rest lengths are the initial
+    distances (derived by the solver), or rest_scale times them."""
+    xs = np.linspace(0.0, size, nx)
+    zs = np.linspace(0.0, size * (ny - 1) / max(1, nx - 1), ny)
+    v = np.array([[x, 0.0, z] for z in zs for x in xs], np.float64)
+    pairs = net_pairs(nx, ny, shear)
+    pins = np.array([0, nx - 1, (ny - 1) * nx, ny * nx - 1], np.int32)
+    rest = None if rest_scale is None else float(rest_scale) * pair_lengths(v, pairs)
+    return Scene(x=v, masses=np.full(len(v), float(node_mass)), groups=[], pin_idx=pins, pin_pts=v[pins].copy(),
+                 pin_vel=np.zeros((4, 3)), variant=VARIANT_H, gravity=gravity, iters=iters, aa_m=aa_m, accel=accel,
+                 n_steps=n_steps, penalty=penalty, name=f"spring_net{nx}x{ny}", springs=[(pairs, float(k), rest, int(mode))])
+
+
+def stitched_panels(n=4, *, gap=0.05, k=20.0, bend=1e-2, size=0.5, iters=30, aa_m=6, accel=1, n_steps=3) -> Scene:
+    """Demo of a seam: two tri_grid(n, n) cloth panels of side `size` side by side in the x-z plane,
+    `gap` apart, cloth()'s membrane and hinges of stiffness `bend` on each, sewn along the facing
+    edges by zero-length springs of stiffness k (stitches); the far edge of the first panel is held
+    by its two corners. Springs, triangles and hinges in one solver."""
+    v, t = tri_grid(n, n, size)
+    nv = len(v)
+    x = np.concatenate([v, v + np.array([size + gap, 0.0, 0.0])])
+    tris = np.concatenate([t, t + nv]).astype(np.int32)
+    pairs = np.array([[j * (n + 1) + n, nv + j * (n + 1)] for j in range(n + 1)], np.int32)
+    pins = np.array([0, n * (n + 1)], np.int32)
+    return Scene(x=x, masses=tri_masses(x, tris, 1.0), groups=[ElementGroup(TRI, LINEAR, 50.0, 0.1, tris, 0.95, 1.05)],
+                 pin_idx=pins, pin_pts=x[pins].copy(), pin_vel=np.zeros((2, 3)), variant=VARIANT_H, iters=iters, aa_m=aa_m,
+                 accel=accel, n_steps=n_steps, name="stitched_panels",
+                 bending=None if bend is None else [(tris, float(bend), True)],
+                 springs=[(pairs, float(k), np.zeros(len(pairs)), SPRING)])
+
+
+def tethered_cloth(nx=8, ny=8, *, k=50.0, size=1.0, slack=0.02, pull=0.06, obstacle=True, collide_radius=0.25, friction=0.5, drop=0.03, iters=30, aa_m=6,
+                   accel=1, n_steps=8, bend=None) -> Scene:
+    """Demo of long-range attachments: a tri_grid(nx, ny) cloth (cloth()'s membrane) in the x-z
+    plane, its x = 0 edge pinned, with one hard tether (SPRING_HARD | SPRING_TETHER, weight sqrt(k))
+    from every pinned node straight across to the free edge, (1 + slack) times as long as the cloth
+    is wide: the free edge cannot move further from the pinned one than that however the soft
+    membrane stretches (its own strain limit is 1.05). pull: the sheet starts pulled out along x,
+    by nothing at its z = 0 side and by `pull` at the other (the rest shape is the square sheet), so
+    the tethers on that side are taut from the first iteration and the others slack. obstacle: a
+    torus (mesh obstacle, Coulomb coefficient `friction`, contacts recorded) lies `drop` under the
+    sheet and catches it as it swings down. collide_radius: the collision-checked nodes are those
+    within this distance (times size, in the rest sheet) of the torus' axis -- the patch that
+    reaches the tube first; None = every free node. A collision term carries the reference's weight
+    sqrt(2 k_soft_rubber) = 5.7e3 whether it touches or not, against the tethers' sqrt(k) = 7: with
+    all 72 free nodes checked 30 iterations leave comb at 1e-1 and a taut tether 4 to 10 % long (200
+    iterations: 7 %), with the default patch of 10 nodes 3.5e-8."""
+    rest, t = tri_grid(nx, ny, size)
+    v = rest.copy()
+    v[:, 0] *= 1.0 + pull * rest[:, 2] / rest[:, 2].max()
+    pins = np.nonzero(v[:, 0] <= 0.5 * size / nx)[0].astype(np.int32)
+    pairs = np.array([[j * (nx + 1), j * (nx + 1) + nx] for j in range(ny + 1)], np.int32)
+    sc = Scene(x=v, masses=tri_masses(rest, t, 1.0), groups=[ElementGroup(TRI, LINEAR, 50.0, 0.1, t, 0.95, 1.05)],
+               pin_idx=pins, pin_pts=v[pins].copy(), pin_vel=np.zeros((len(pins), 3)), variant=VARIANT_H, iters=iters,
+               aa_m=aa_m, accel=accel, n_steps=n_steps, name="tethered_cloth", rest=rest,
+               bending=None if bend is None else [(t, float(bend), True)],
+               springs=[(pairs, float(k), (1.0 + slack) * pair_lengths(rest, pairs), SPRING_HARD | SPRING_TETHER)])
+    if obstacle:
+        R, r = 0.25 * size, 0.1 * size
+        ctr = (0.6 * size, -(r + drop), 0.5 * size * ny / nx)
+        sc.mesh_obstacles = [torus_mesh(16, 8, R, r, ctr)]
+        near = np.setdiff1d(np.arange(sc.n_nodes, dtype=np.int32), pins).astype(np.int32)
+        if collide_radius is not None:
+            d = np.hypot(rest[near, 0] - ctr[0], rest[near, 2] - ctr[2])
+            near = near[d < collide_radius * size]
+        sc.collision_idx = near.astype(np.int32)
+        sc.obstacle_friction = [float(friction)]
+        sc.record_contacts = True
+    return sc
+
+
+def hanging_block(cells=(2, 2, 2), cell=0.2, material=LINEAR, *, E=1e5, nu=0.3, k=4000.0, hang=0.3, lift=(0.01, 0.005, 0.0),
+                  iters=30, aa_m=6, accel=1, n_steps=6) -> Scene:
+    """Demo of the soft attachment: a tet block (kuhn_tet_blocks, `material`) hanging by four springs
+    of stiffness k from its top corners to four anchor nodes `hang` above them. The anchors are extra
+    nodes in no element, pinned, and move by `lift` per step (pin_vel, i.e. set_pins every step): a
+    handle of finite stiffness that drags the body. Block nodes come first, then the anchors."""
+    bv, bt = kuhn_tet_blocks(*cells)
+    bv = bv * float(cell)
+    nb = len(bv)
+    top, lo, hi = bv[:, 1].max(), bv.min(0), bv.max(0)
+    corners = [int(np.argmin(np.abs(bv - np.array([cx, top, cz])).sum(1))) for cx in (lo[0], hi[0]) for cz in (lo[2], hi[2])]
+    anchors = bv[corners] + np.array([0.0, hang, 0.0])
+    x = np.concatenate([bv, anchors])
+    pins = np.arange(nb, nb + 4, dtype=np.int32)
+    pairs = np.array([[nb + i, c] for i, c in enumerate(corners)], np.int32)
+    return Scene(x=x, masses=np.concatenate([tet_masses(bv, bt, 1522.0), np.ones(4)]),
+                 groups=[ElementGroup(TET, int(material), E, nu, bt)], pin_idx=pins, pin_pts=anchors.copy(),
+                 pin_vel=np.tile(np.asarray(lift, np.float64), (4, 1)), variant=VARIANT_H, iters=iters, aa_m=aa_m,
+                 accel=accel, n_steps=n_steps, name="hanging_block", springs=[(pairs, float(k), None, SPRING)])
 
 
 def cantilever(cx=20, cy=4, cz=5, material=NEOHOOKEAN, *, variant=VARIANT_X, aa_m=6, iters=50,

@@ -131,6 +131,28 @@ int aa_elastic_add_tris_var(aa_elastic h, const double* verts3, const int* tris3
  * AA_VARIANT_Z and one partitioned over more than one rank. */
 int aa_elastic_add_bending(aa_elastic h, const double* verts3, const int* tris3, int n_tris, double k_bend,
                            int flat_rest, int vertex_offset, int* n_hinges);
+/* Springs, tethers and struts (no counterpart in the reference, whose SpringPin is an infinitely hard
+ * spring on one node): spring e joins nodes a != b = pairs2[2e], pairs2[2e + 1] (+ vertex_offset).
+ * Its reduction row is (-1, +1), so z = x_b - x_a in R^3: two vertices, one column. Rest length
+ * L = rest[e] >= 0 (rest == NULL: |verts3[b] - verts3[a]|) and stiffness k[e] > 0 per spring; ADMM
+ * weight sqrt(k). One mode per call (one group per call). With n = |v| = sqrt((v0^2 + v1^2) + v2^2)
+ * the prox z = argmin U(z) + 1/2 k |z - v|^2 is z = s v:
+ *   AA_SPRING          U = 1/2 k (|z| - L)^2          s = 1/2 + 1/2 (L / n)
+ *   AA_SPRING_TETHER   U = 1/2 k max(0, |z| - L)^2    n <= L: z = v bitwise; else as AA_SPRING
+ *   AA_SPRING_STRUT    U = 1/2 k max(0, L - |z|)^2    n >= L: z = v bitwise; else as AA_SPRING
+ *   ... | AA_SPRING_HARD   U the indicator of |z| = L / |z| <= L / |z| >= L, k sets the weight only:
+ *                          s = L / n where the soft form would act, z = v bitwise elsewhere
+ * n = 0 has no direction: z = v in every mode (stated, not derived). L = 0 is allowed: a zero-length
+ * spring is a stitch, its hard two-sided form a weld. Parallel springs on one pair are allowed. An
+ * endpoint may be pinned; a pinned endpoint moved by aa_elastic_set_pins every step is a soft
+ * attachment. Before initialize only (AA_ERR_STATE after). AA_ERR_ARG naming the first offending
+ * spring: an index out of range, a == b, k not finite or not > 0, rest negative or not finite; also
+ * an unknown mode, a null array with n_springs > 0, rest == NULL together with verts3 == NULL. A
+ * refused call changes nothing. initialize refuses a solver with springs in AA_VARIANT_Z and one
+ * partitioned over more than one rank. */
+enum { AA_SPRING = 0, AA_SPRING_TETHER = 1, AA_SPRING_STRUT = 2, AA_SPRING_HARD = 4 };
+int aa_elastic_add_springs(aa_elastic h, const double* verts3, const int* pairs2, int n_springs, int mode,
+                           const double* k /* [n] */, const double* rest /* [n] or NULL */, int vertex_offset);
 /* Solver::set_pins(inds, points): points3 == NULL pins in place (Solver.cpp:280-315). */
 int aa_elastic_set_pins(aa_elastic h, const int* inds, const double* points3, int n_pins);
 
@@ -564,7 +586,7 @@ int aa_geom_set_comm(aa_geom h, aa_comm c);
  *     1 NeoHookeanTet / 2 StVKTet prox (L-BFGS, TetEnergyTerm.cpp:151-162; prm4 = E, nu, h with
  *     vol = h^3/6; iters = L-BFGS iterations, -1 on a line-search failure), 3 / 4 TriEnergyTerm
  *     prox of the H / X solver copy (6 per tri; prm4[2..3] = limit_min, limit_max), 5 the bending
- *     hinge's prox (3 per hinge; prm4[0] = r)
+ *     hinge's prox (3 per hinge; prm4[0] = r), 6 the spring's prox (3 per spring; prm4 = L, mode)
  *   aa_test_cod_solve: the Anderson normal-equation solve (Eigen CompleteOrthogonalDecomposition,
  *     AndersonAcceleration.h:186-188) of a k x k column-major M
  *   aa_test_geom_project: Constraint::project_impl of plane (k 3..8) / angle (k 3) / edge (k 2)

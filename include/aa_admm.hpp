@@ -58,7 +58,7 @@ public:
 class EnergyTerm {
 public:
     virtual ~EnergyTerm() {}
-    int kind = 0, material = AA_LINEAR;   // kind 0 tet, 1 tri, 3 bending hinges (BendingEnergyTerm)
+    int kind = 0, material = AA_LINEAR;   // kind 0 tet, 1 tri, 3 bending hinges (BendingEnergyTerm), 4 springs (SpringEnergyTerm)
     Lame lame;
     std::vector<Lame> lames;     // per-element materials ([count]); empty: `lame` for every element
     std::vector<double> verts;   // rest shape (as given to create_*_from_mesh)
@@ -141,6 +141,36 @@ inline void create_bending_from_mesh(std::vector<std::shared_ptr<EnergyTerm>>& e
     e->verts.assign(verts, verts + 3 * (size_t)nv);
     e->inds.assign(inds, inds + 3 * (size_t)n_tris);
     e->count = n_tris;
+    e->vertex_offset = vertex_offset;
+    energyterms.push_back(e);
+}
+
+// Springs, tethers and struts (aa_elastic_add_springs; the reference's SpringPin is a hard spring on
+// one node): n two-node springs pairs[2e], pairs[2e + 1] with stiffness k[e] and rest length rest[e];
+// rest null takes the distance of the pair in verts (verts may be null when rest is given). mode:
+// AA_SPRING / AA_SPRING_TETHER / AA_SPRING_STRUT, | AA_SPRING_HARD.
+class SpringEnergyTerm : public EnergyTerm {
+public:
+    std::vector<double> k, rest;   // rest empty: lengths from verts
+    int mode = AA_SPRING;
+    bool has_verts = false;
+};
+template <typename IN_SCALAR>
+inline void create_springs(std::vector<std::shared_ptr<EnergyTerm>>& energyterms, const IN_SCALAR* verts, const int* pairs,
+                           int n, const double* k, const double* rest, int mode, const int vertex_offset) {
+    auto e = std::make_shared<SpringEnergyTerm>();
+    e->kind = 4;
+    e->mode = mode;
+    e->k.assign(k, k + n);
+    if (rest) e->rest.assign(rest, rest + n);
+    if (verts) {
+        int nv = 0;
+        for (int i = 0; i < 2 * n; ++i) nv = std::max(nv, pairs[i] + 1);
+        e->verts.assign(verts, verts + 3 * (size_t)nv);
+        e->has_verts = true;
+    }
+    e->inds.assign(pairs, pairs + 2 * (size_t)n);
+    e->count = n;
     e->vertex_offset = vertex_offset;
     energyterms.push_back(e);
 }
@@ -440,6 +470,9 @@ public:
                 if (const BendingEnergyTerm* b = dynamic_cast<const BendingEnergyTerm*>(e.get())) {
                     rc = aa_elastic_add_bending(h_, b->verts.data(), b->inds.data(), b->count, b->k_bend, b->flat_rest ? 1 : 0,
                                                 b->vertex_offset, nullptr);
+                } else if (const SpringEnergyTerm* sp = dynamic_cast<const SpringEnergyTerm*>(e.get())) {
+                    rc = aa_elastic_add_springs(h_, sp->has_verts ? sp->verts.data() : nullptr, sp->inds.data(), sp->count, sp->mode,
+                                                sp->k.data(), sp->rest.empty() ? nullptr : sp->rest.data(), sp->vertex_offset);
                 } else if (!e->lames.empty()) {   // per-element materials: the _var calls
                     std::vector<aa_lame> ls;
                     for (auto& le : e->lames) ls.push_back(le.c());
