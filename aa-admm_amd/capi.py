@@ -24,7 +24,7 @@ EXPORTS = [
     "aa_last_error", "aa_version", "aa_ctx_create", "aa_ctx_destroy", "aa_ctx_synchronize", "aa_ctx_bench_read",
     "aa_ctx_warm_dense", "aa_lame_from_young",
     "aa_settings_default", "aa_elastic_create", "aa_elastic_destroy", "aa_elastic_add_nodes", "aa_elastic_add_tets",
-    "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_add_bending", "aa_elastic_add_springs", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
+    "aa_elastic_add_tris", "aa_elastic_add_tets_var", "aa_elastic_add_tris_var", "aa_elastic_add_bending", "aa_elastic_add_springs", "aa_elastic_add_ties", "aa_closest_on_triangles", "aa_elastic_set_pins", "aa_elastic_initialize", "aa_elastic_step",
     "aa_elastic_add_obstacle", "aa_elastic_add_mesh_obstacle", "aa_elastic_set_mesh_obstacle_pose",
     "aa_elastic_get_mesh_obstacle_pose", "aa_elastic_set_mesh_obstacle_vertices", "aa_elastic_get_mesh_obstacle_vertices",
     "aa_elastic_bind_mesh_obstacle", "aa_elastic_mesh_obstacle_status", "aa_elastic_set_mesh_obstacle_exempt",
@@ -364,6 +364,28 @@ class Solver:
         _chk(lib().aa_elastic_add_springs(self.h, None if v is None else _dp(v), _ip(p), C.c_int(n), C.c_int(int(mode)), _dp(kk),
                                           None if r is None else _dp(r), C.c_int(vertex_offset)))
 
+    def add_ties(self, nodes_a, w_a, nodes_b, w_b, k, rest=None, mode=AA_SPRING, verts=None, vertex_offset=0):
+        """Ties between barycentric anchors (aa_elastic_add_ties): nodes_a / w_a (n, na), nodes_b / w_b
+        (n, nb), 1 <= na, nb <= 4 and 3 <= na + nb <= 6; anchor = sum of weight x node, weights used as
+        given. Stiffness k (a scalar is broadcast), rest lengths rest (n,) or None = the anchors'
+        distances in verts (default: the solver's current node positions). mode as for add_springs.
+        Before initialize."""
+        wa, wb = np.asarray(w_a, np.float64), np.asarray(w_b, np.float64)
+        if wa.ndim != 2 or wb.ndim != 2 or len(wa) != len(wb):
+            raise ValueError("add_ties: w_a (n, na) and w_b (n, nb) with the same n")
+        n, na, nb = wa.shape[0], wa.shape[1], wb.shape[1]
+        ia = np.ascontiguousarray(np.asarray(nodes_a, np.int32).reshape(n, na))
+        ib = np.ascontiguousarray(np.asarray(nodes_b, np.int32).reshape(n, nb))
+        wa, wb = np.ascontiguousarray(wa), np.ascontiguousarray(wb)
+        kk = np.ascontiguousarray(np.broadcast_to(np.asarray(k, np.float64), (n,)))
+        r = None if rest is None else np.ascontiguousarray(np.broadcast_to(np.asarray(rest, np.float64), (n,)))
+        if verts is None and rest is None:
+            verts = self.x
+        v = None if verts is None else np.ascontiguousarray(verts, np.float64).reshape(-1)
+        _chk(lib().aa_elastic_add_ties(self.h, None if v is None else _dp(v), C.c_int(na), _ip(ia), _dp(wa), C.c_int(nb), _ip(ib),
+                                       _dp(wb), C.c_int(n), C.c_int(int(mode)), _dp(kk), None if r is None else _dp(r),
+                                       C.c_int(vertex_offset)))
+
     def set_pins(self, inds, points=None):
         i = np.ascontiguousarray(inds, np.int32).reshape(-1)
         if points is None:
@@ -683,6 +705,8 @@ def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
         s.add_bending(scene.rest_x, tris, k_bend, flat_rest)
     for pairs, k, rest, mode in getattr(scene, "springs", None) or []:   # after the bending entries
         s.add_springs(pairs, k, rest, mode, verts=scene.rest_x)
+    for nodes_a, w_a, nodes_b, w_b, k, rest, mode in getattr(scene, "ties", None) or []:   # after the springs
+        s.add_ties(nodes_a, w_a, nodes_b, w_b, k, rest, mode, verts=scene.rest_x)
     s.set_pins(scene.pin_idx, scene.pin_pts)
     for kind, prm in getattr(scene, "obstacles", []):
         s.add_obstacle(kind, prm)
@@ -707,6 +731,33 @@ def solver_from_scene(ctx: Context, scene, comm=None) -> Solver:
         if on:
             s.set_mesh_obstacle_carry(m, True)
     return s
+
+
+def closest_on_triangles(ctx: Context, V, F, Q):
+    """Where the queries Q (n, 3) land on the triangle list (V, F) (aa_closest_on_triangles; any list,
+    open or non-manifold): (closest points (n, 3), triangle (n,) in F's numbering, barycentric
+    weights (n, 3) of the closest point on that triangle's corners)."""
+    v = np.ascontiguousarray(V, np.float64).reshape(-1)
+    f = np.ascontiguousarray(F, np.int32).reshape(-1)
+    q = np.ascontiguousarray(Q, np.float64).reshape(-1, 3)
+    n = q.shape[0]
+    c, tri, b = np.zeros((n, 3)), np.zeros(n, np.int32), np.zeros((n, 3))
+    _chk(lib().aa_closest_on_triangles(ctx.h, _dp(v), C.c_int(len(v) // 3), _ip(f), C.c_int(len(f) // 3), _dp(q), C.c_int(n),
+                                       _dp(c), _ip(tri), _dp(b)))
+    return c, tri, b
+
+
+def ties_to_surface(ctx: Context, x, nodes, F, k, mode=AA_SPRING, rest=None):
+    """Ties from the nodes `nodes` to where they land on the surface (x, F): the query runs for
+    x[nodes] against (x, F), and the result is a Scene.ties entry (nodes_a, w_a, nodes_b, w_b, k, rest,
+    mode) with na = 3 (the triangle's corners, the query's barycentric weights) and nb = 1 (the node,
+    weight 1). The triangles must not contain the tied nodes (a tie names no node twice). rest = None:
+    the distance at binding time."""
+    x = np.asarray(x, np.float64).reshape(-1, 3)
+    nodes = np.asarray(nodes, np.int32).reshape(-1)
+    F = np.asarray(F, np.int32).reshape(-1, 3)
+    _, tri, b = closest_on_triangles(ctx, x, F, x[nodes])
+    return (F[tri].astype(np.int32), b, nodes.reshape(-1, 1), np.ones((len(nodes), 1)), k, rest, int(mode))
 
 
 def settings_from_scene(scene) -> Settings:

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/aa_admm.h"
+#include "closest_query.hpp"
 #include "comm.hpp"
 #include "dense_gpu.hpp"
 #include "elastic.hpp"
@@ -194,6 +195,15 @@ int aa_elastic_add_springs(aa_elastic h, const double* verts3, const int* pairs2
     return guarded([&] {
         NEED(h, "null handle");
         h->s->add_springs(verts3, pairs2, n_springs, mode, k, rest, vertex_offset);
+    });
+}
+
+int aa_elastic_add_ties(aa_elastic h, const double* verts3, int na, const int* nodes_a, const double* w_a, int nb,
+                        const int* nodes_b, const double* w_b, int n_ties, int mode, const double* k, const double* rest,
+                        int vertex_offset) {
+    return guarded([&] {
+        NEED(h, "null handle");
+        h->s->add_ties(verts3, na, nodes_a, w_a, nb, nodes_b, w_b, n_ties, mode, k, rest, vertex_offset);
     });
 }
 
@@ -656,6 +666,35 @@ int aa_geom_kernel_stats(aa_geom h, const char* name, double* avg_ms, double* by
     return guarded([&] {
         NEED(h && name, "null argument");
         if (!h->s->kernel_stats(name, avg_ms, bytes, launches)) throw aa::Error(AA_ERR_ARG, std::string("no kernel class ") + name);
+    });
+}
+
+int aa_closest_on_triangles(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris, const double* q3,
+                            int n, double* closest3, int* tri, double* bary3) {
+    return guarded([&] {
+        NEED(ctx, "null context");
+        NEED(n >= 0 && (n == 0 || q3), "closest_on_triangles: bad argument");
+        const aa::ClosestSurfaceHost M = aa::prepare_closest_surface(verts3, n_verts, tris3, n_tris);
+        aa::validate_closest_queries(q3, n);
+        if (n == 0) return;
+        AA_HIP(hipSetDevice(ctx->c.device));
+        hipStream_t s = ctx->c.stream;
+        aa::DevBuf<aa::BvhNode> nodes;
+        aa::DevBuf<aa::BvhTri> tris;
+        aa::DevBuf<int> orig, dt(n);
+        aa::DevBuf<double> dq, dc((size_t)3 * n), db((size_t)3 * n);
+        nodes.upload(M.nodes, s);
+        tris.upload(M.tris, s);
+        orig.upload(M.orig, s);
+        dq.upload(q3, (size_t)3 * n, s);
+        aa::SurfDev S{};
+        S.nodes = nodes.p; S.tris = tris.p;
+        S.n_nodes = (int)M.nodes.size(); S.n_tris = (int)M.tris.size();
+        aa::launch_closest_on_triangles(S, orig.p, dq.p, n, dc.p, dt.p, db.p, s);
+        if (closest3) AA_HIP(hipMemcpyAsync(closest3, dc.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+        if (tri) AA_HIP(hipMemcpyAsync(tri, dt.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+        if (bary3) AA_HIP(hipMemcpyAsync(bary3, db.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+        AA_HIP(hipStreamSynchronize(s));
     });
 }
 

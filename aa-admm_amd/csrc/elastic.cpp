@@ -197,6 +197,28 @@ void ElasticSolver::add_springs(const double* verts3, const int* pairs2, int n_s
     hgroups_.push_back(std::move(g));
 }
 
+// Ties (ties.hpp): one group of kind 5, na + nb vertices and the one column z = p_B - p_A per tie,
+// w = sqrt(k); the rest length L rides in `vol`, the mode in `material`.
+void ElasticSolver::add_ties(const double* verts3, int na, const int* nodes_a, const double* w_a, int nb, const int* nodes_b,
+                             const double* w_b, int n_ties, int mode, const double* k, const double* rest, int vertex_offset) {
+    if (initialized_) throw Error(ERR_STATE, "add_ties: adding energy terms after initialize is not supported");
+    // an index is in range when its node exists: node + vertex_offset in [0, num_nodes)
+    const TieSet S = build_ties(verts3, num_nodes() - vertex_offset, na, nodes_a, w_a, nb, nodes_b, w_b, n_ties, mode, k, rest);
+    for (int e = 0; e < n_ties; ++e)
+        for (int a = 0; a < S.nv; ++a)
+            if (S.idx[(size_t)S.nv * e + a] + vertex_offset < 0)
+                throw Error(ERR_ARG, "add_ties: tie " + std::to_string(e) + " has a node index out of range");
+    HostGroup g;
+    g.kind = 5; g.material = mode; g.lame = aa_lame{};
+    g.nv = S.nv; g.ncol = 1;
+    g.idx.resize(S.idx.size());
+    for (size_t i = 0; i < g.idx.size(); ++i) g.idx[i] = S.idx[i] + vertex_offset;
+    g.G = S.G;
+    g.vol = S.L;
+    g.w = S.w;
+    hgroups_.push_back(std::move(g));
+}
+
 void ElasticSolver::HostGroup::append_element(const HostGroup& from, size_t t) {
     idx.insert(idx.end(), from.idx.begin() + t * nv, from.idx.begin() + (t + 1) * nv);
     G.insert(G.end(), from.G.begin() + t * ncol * nv, from.G.begin() + (t + 1) * ncol * nv);
@@ -565,6 +587,11 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
         throw Error(ERR_ARG, "initialize: springs exist in the (u,x) variant only (the z variant's gradient step has no spring term)");
     if (springs && comm_ && comm_->size() > 1)
         throw Error(ERR_ARG, "initialize: the solver has springs and is partitioned over " + std::to_string(comm_->size()) + " ranks (springs need one rank)");
+    const bool ties = std::any_of(hgroups_.begin(), hgroups_.end(), [](const HostGroup& g) { return g.kind == 5; });
+    if (ties && st_.variant == AA_VARIANT_Z)
+        throw Error(ERR_ARG, "initialize: ties exist in the (u,x) variant only (the z variant's gradient step has no tie term)");
+    if (ties && comm_ && comm_->size() > 1)
+        throw Error(ERR_ARG, "initialize: the solver has ties and is partitioned over " + std::to_string(comm_->size()) + " ranks (ties need one rank)");
     if (st_.variant == AA_VARIANT_Z && !coll_nodes_.empty())
         throw Error(ERR_ARG, "set_collisions: energy-based collisions exist in the (u,x) variant only (admm_anderson_hard_zxu)");
     // collision terms (Solver.cpp:386-392): after the other terms, one per node in node order;
@@ -993,7 +1020,7 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
         const double per = 4.0 * g.d.nv + 8.0 * g.d.ncol * g.d.nv + 8.0;
         lz += g.d.count * (per + 2 * 8.0 * g.d.dim + 28.0 * g.d.nv);   // u in, z out, slot positions + slots out
         if (g.var) lz += g.d.count * (g.d.kind == 1 ? 16.0 : g.d.mat != 0 ? 24.0 : 0.0);   // per-element materials
-        if (g.d.kind == 3 || g.d.kind == 4) lz += g.d.count * 8.0;   // a hinge's or a spring's rest length
+        if (g.d.kind >= 3 && g.d.kind <= 5) lz += g.d.count * 8.0;   // a hinge's, a spring's or a tie's rest length
         rs += g.d.count * (per + 3 * 8.0 * g.d.dim);
     }
     kstats_["local_z"].bytes = lz + 24.0 * n;

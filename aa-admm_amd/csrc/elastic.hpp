@@ -17,6 +17,7 @@
 #include "mesh_obstacle.hpp"
 #include "mesh_refit.hpp"
 #include "springs.hpp"
+#include "ties.hpp"
 
 namespace aa {
 
@@ -79,6 +80,9 @@ public:
     // two-node springs (springs.hpp): one group of kind 4 per call; node ids pairs2 + vertex_offset
     void add_springs(const double* verts3, const int* pairs2, int n_springs, int mode, const double* k, const double* rest,
                      int vertex_offset);
+    // ties between barycentric anchors (ties.hpp): one group of kind 5 per call; node ids + vertex_offset
+    void add_ties(const double* verts3, int na, const int* nodes_a, const double* w_a, int nb, const int* nodes_b,
+                  const double* w_b, int n_ties, int mode, const double* k, const double* rest, int vertex_offset);
     void set_pins(const int* inds, const double* pts3, int n);
     // energy-based collisions of the (u,x) variant (admm_anderson_hard_zxu Solver.cpp:318-348)
     void add_obstacle(int type, const double* params);
@@ -158,7 +162,7 @@ public:
 
 private:
     struct HostGroup {
-        int kind, material, nv, ncol;   // kind 3 (bending hinge): G holds K, vol the rest length r; kind 4 (spring): G = (-1, +1), vol = L, material = the mode
+        int kind, material, nv, ncol;   // kind 3 (bending hinge): G holds K, vol the rest length r; kind 4 (spring): G = (-1, +1), vol = L, material = the mode; kind 5 (tie): G = (-a, +b), nv = na + nb, else as a spring
         aa_lame lame;
         std::vector<int> idx;       // [count][nv] global node ids
         std::vector<double> G;      // [count][ncol][nv]

@@ -246,12 +246,14 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
         double F[D], Cp[D], uu[D], vin[D], zz[D];
         gather_F<S>(g, e, xfull, nf, F, Cp);
         const double w = g.w[e];
-        double rest = 0.0;   // the hinge's r / the spring's L, with the other loads
-        if constexpr (S == kShapeHinge || S == kShapeSpring) rest = g.vol[e];
+        double rest = 0.0;   // the hinge's r / the spring's or tie's L, with the other loads
+        if constexpr (S == kShapeHinge || S == kShapeSpring || shape_is_tie(S)) rest = g.vol[e];
         load_u<D>(g, e, u, uu);
 #pragma unroll
         for (int i = 0; i < D; ++i) vin[i] = F[i] + uu[i] / w;
-        if constexpr (NV == 1) {
+        if constexpr (shape_is_tie(S)) {   // first: a tie has 3..6 vertices, none of the simplex branches is its
+            dev::spring_prox(vin, rest, g.mat, zz);
+        } else if constexpr (NV == 1) {
             // the (u,x) variant's candidate exactly as EnergyTerm::update_z forms it for an identity
             // row (EnergyTerm.hpp:166-178: z = W^-1 (W x + u - c), W^-1 stored as 1/w): the
             // contact decision is discrete, so the candidate is rounded like the reference's
@@ -819,8 +821,9 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
                                                     V... gvp) {
     constexpr bool VAR = kVar<V...>;
     if (gated(ctrl, redo)) return;
-    // (a hinge or a spring counts as a shape of its own below: NV is 0 for it, none of the simplex branches)
-    constexpr int NV = S == kShapeHinge || S == kShapeSpring ? 0 : shape_nv(S), D = 3 * shape_nc(S);
+    // (a hinge, a spring or a tie counts as a shape of its own below: NV is 0 for it, none of the simplex branches)
+    constexpr bool ONE_COL = S == kShapeHinge || S == kShapeSpring || shape_is_tie(S);
+    constexpr int NV = ONE_COL ? 0 : shape_nv(S), D = 3 * shape_nc(S);
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= g.count) return;
     // the gradient (mode 1) needs only z: it runs before the element's gathers, so its
@@ -842,9 +845,9 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
     }
     if (mode == 1) {
         double gr[D];
-        if constexpr (NV == 3 || NV == 1 || S == kShapeHinge || S == kShapeSpring) {
-            // TriEnergyTerm::get_gradient / Collision::get_gradient throw in the reference; a hinge
-            // or spring group is refused in the Z variant (initialize), so mode 1 never reaches it
+        if constexpr (NV == 3 || NV == 1 || ONE_COL) {
+            // TriEnergyTerm::get_gradient / Collision::get_gradient throw in the reference; a hinge,
+            // spring or tie group is refused in the Z variant (initialize), so mode 1 never reaches it
             if (ctrl) ctrl->fail = 2;
 #pragma unroll
             for (int i = 0; i < D; ++i) gr[i] = 0;
@@ -1919,7 +1922,13 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
         AA_CHECK_LAUNCH();
         return;
     }
-    if (g.kind == 4) hipLaunchKernelGGL((k_local_z<kShapeSpring, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+    if (g.kind == 5) {   // ties: one instantiation per vertex count
+        if (g.nv == 3) hipLaunchKernelGGL((k_local_z<shape_tie(3), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+        else if (g.nv == 4) hipLaunchKernelGGL((k_local_z<shape_tie(4), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+        else if (g.nv == 5) hipLaunchKernelGGL((k_local_z<shape_tie(5), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+        else hipLaunchKernelGGL((k_local_z<shape_tie(6), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+    }
+    else if (g.kind == 4) hipLaunchKernelGGL((k_local_z<kShapeSpring, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
     else if (g.kind == 3) hipLaunchKernelGGL((k_local_z<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
     else if (g.kind == 2 && meshes) hipLaunchKernelGGL((k_local_z<1, 0, const MeshObsDev*>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, meshes);
     else if (g.kind == 2) hipLaunchKernelGGL((k_local_z<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
@@ -1959,7 +1968,13 @@ void launch_resid_update_u(const GroupDev& g, const double* xfull, const double*
                            int nf, Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 4) hipLaunchKernelGGL(k_resid_u<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+    if (g.kind == 5) {   // ties: one instantiation per vertex count
+        if (g.nv == 3) hipLaunchKernelGGL(k_resid_u<shape_tie(3)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+        else if (g.nv == 4) hipLaunchKernelGGL(k_resid_u<shape_tie(4)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+        else if (g.nv == 5) hipLaunchKernelGGL(k_resid_u<shape_tie(5)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+        else hipLaunchKernelGGL(k_resid_u<shape_tie(6)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+    }
+    else if (g.kind == 4) hipLaunchKernelGGL(k_resid_u<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
     else if (g.kind == 3) hipLaunchKernelGGL(k_resid_u<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
     else if (g.kind == 2) hipLaunchKernelGGL(k_resid_u<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
     else if (g.kind == 1) hipLaunchKernelGGL(k_resid_u<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
@@ -1971,7 +1986,13 @@ void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, con
                     int nf, int mode, int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 4) hipLaunchKernelGGL((k_u_and_y<kShapeSpring, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+    if (g.kind == 5) {   // ties: one instantiation per vertex count
+        if (g.nv == 3) hipLaunchKernelGGL((k_u_and_y<shape_tie(3), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+        else if (g.nv == 4) hipLaunchKernelGGL((k_u_and_y<shape_tie(4), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+        else if (g.nv == 5) hipLaunchKernelGGL((k_u_and_y<shape_tie(5), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+        else hipLaunchKernelGGL((k_u_and_y<shape_tie(6), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+    }
+    else if (g.kind == 4) hipLaunchKernelGGL((k_u_and_y<kShapeSpring, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
     else if (g.kind == 3) hipLaunchKernelGGL((k_u_and_y<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
     else if (g.kind == 2) hipLaunchKernelGGL((k_u_and_y<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
     else if (g.kind == 1) hipLaunchKernelGGL((k_u_and_y<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);   // no material reads
@@ -1986,7 +2007,13 @@ void launch_prim_z(const GroupDev& g, const double* xfull, const double* z, cons
                    Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 4) hipLaunchKernelGGL(k_prim_z<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+    if (g.kind == 5) {   // ties: one instantiation per vertex count
+        if (g.nv == 3) hipLaunchKernelGGL(k_prim_z<shape_tie(3)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+        else if (g.nv == 4) hipLaunchKernelGGL(k_prim_z<shape_tie(4)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+        else if (g.nv == 5) hipLaunchKernelGGL(k_prim_z<shape_tie(5)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+        else hipLaunchKernelGGL(k_prim_z<shape_tie(6)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+    }
+    else if (g.kind == 4) hipLaunchKernelGGL(k_prim_z<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
     else if (g.kind == 3) hipLaunchKernelGGL(k_prim_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
     else if (g.kind == 2) hipLaunchKernelGGL(k_prim_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
     else if (g.kind == 1) hipLaunchKernelGGL(k_prim_z<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
@@ -1997,7 +2024,13 @@ void launch_prim_z(const GroupDev& g, const double* xfull, const double* z, cons
 void launch_init_z(const GroupDev& g, const double* xfull, double* z, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 4) hipLaunchKernelGGL(k_init_z<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+    if (g.kind == 5) {   // ties: one instantiation per vertex count
+        if (g.nv == 3) hipLaunchKernelGGL(k_init_z<shape_tie(3)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+        else if (g.nv == 4) hipLaunchKernelGGL(k_init_z<shape_tie(4)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+        else if (g.nv == 5) hipLaunchKernelGGL(k_init_z<shape_tie(5)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+        else hipLaunchKernelGGL(k_init_z<shape_tie(6)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+    }
+    else if (g.kind == 4) hipLaunchKernelGGL(k_init_z<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
     else if (g.kind == 3) hipLaunchKernelGGL(k_init_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
     else if (g.kind == 2) hipLaunchKernelGGL(k_init_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
     else if (g.kind == 1) hipLaunchKernelGGL(k_init_z<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);

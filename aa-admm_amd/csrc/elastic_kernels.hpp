@@ -11,8 +11,8 @@ constexpr double kCombEps = 1e-20; // Solver.cpp:93 eps
 
 // One homogeneous block of energy terms (same kind / material / Lame), SoA on device.
 struct GroupDev {
-    int kind;            // 0 tet, 1 tri, 2 collision point (CollisionEnergyTerm.hpp:41-117), 3 bending hinge, 4 spring
-    int mat;             // 0 linear, 1 NeoHookean, 2 StVK; kind 4: the spring mode (AA_SPRING_*)
+    int kind;            // 0 tet, 1 tri, 2 collision point (CollisionEnergyTerm.hpp:41-117), 3 bending hinge, 4 spring, 5 tie
+    int mat;             // 0 linear, 1 NeoHookean, 2 StVK; kinds 4, 5: the spring mode (AA_SPRING_*)
     int count;           // elements
     int nv, ncol, dim;   // 4/3/9 for tets, 3/2/6 for tris
     int pinned;          // some element of the group has a pinned node (C_fix terms exist)
@@ -68,7 +68,14 @@ constexpr int kShapeHinge = 16 * 4 + 1;
 // kShapeSpring: the two-node spring (GroupDev::kind 4), row (-1, +1), the one column z = x_b - x_a;
 // its rest length L[count] rides in GroupDev::vol like the hinge's r, its mode in GroupDev::mat.
 constexpr int kShapeSpring = 16 * 2 + 1;
-__host__ __device__ constexpr int shape_nv(int s) { return s < 16 ? s : s / 16; }
+// shape_tie(nv): a tie (GroupDev::kind 5, ties.hpp), nv = na + nb = 3..6 vertices and the one column
+// z = sum_j b_j x_Bj - sum_i a_i x_Ai (row (-a, +b) in G); L in GroupDev::vol and the mode in
+// GroupDev::mat as for a spring. 16 * 4 + 1 is the hinge already, so a tie carries a tag above bit 8,
+// which shape_nv / shape_nc mask off.
+constexpr int kShapeTieTag = 256;
+__host__ __device__ constexpr int shape_tie(int nv) { return kShapeTieTag + 16 * nv + 1; }
+__host__ __device__ constexpr bool shape_is_tie(int s) { return s >= kShapeTieTag; }
+__host__ __device__ constexpr int shape_nv(int s) { return s < 16 ? s : (s & 255) / 16; }
 __host__ __device__ constexpr int shape_nc(int s) { return s < 16 ? ncol_of(s) : s % 16; }
 
 // Device-side control block: residual bookkeeping, reject/done flags, Anderson state.

@@ -139,6 +139,11 @@ class Scene:
     # (capi.solver_from_scene binds them after the bending entries, Solver.add_springs). Like
     # bending, unknown to the oracle and the reference driver. None = no springs, today's scene.
     springs: Optional[list] = None
+    # ties: a list of (nodes_a (m, na) int32, w_a (m, na), nodes_b (m, nb) int32, w_b (m, nb), k (scalar
+    # or (m,)), rest ((m,), scalar or None = the anchors' distances in rest_x), mode) -- springs between
+    # barycentric anchors, one group per entry (capi.solver_from_scene binds them after the springs,
+    # Solver.add_ties). Unknown to the oracle and the reference driver. None = no ties.
+    ties: Optional[list] = None
 
     @property
     def rest_x(self) -> np.ndarray:
@@ -460,6 +465,102 @@ def hanging_block(cells=(2, 2, 2), cell=0.2, material=LINEAR, *, E=1e5, nu=0.3, 
                  groups=[ElementGroup(TET, int(material), E, nu, bt)], pin_idx=pins, pin_pts=anchors.copy(),
                  pin_vel=np.tile(np.asarray(lift, np.float64), (4, 1)), variant=VARIANT_H, iters=iters, aa_m=aa_m,
                  accel=accel, n_steps=n_steps, name="hanging_block", springs=[(pairs, float(k), None, SPRING)])
+
+
+# ----------------------------------------------------------------------------------------
+# ties: springs between barycentric anchors (Scene.ties)
+# ----------------------------------------------------------------------------------------
+
+def tri_barycentric(A, B, C, P):
+    """Barycentric weights (n, 3) of the points P on the triangles (A, B, C), all (n, 3): Cramer's rule
+    on the edge Gram matrix, the statement of the solver's closest-point query."""
+    d3 = lambda u, w: (u[:, 0] * w[:, 0] + u[:, 1] * w[:, 1]) + u[:, 2] * w[:, 2]
+    e1, e2, d = B - A, C - A, P - A
+    d11, d12, d22, p1, p2 = d3(e1, e1), d3(e1, e2), d3(e2, e2), d3(d, e1), d3(d, e2)
+    den = d11 * d22 - d12 * d12
+    b1 = (d22 * p1 - d12 * p2) / den
+    b2 = (d11 * p2 - d12 * p1) / den
+    return np.stack([(1.0 - b1) - b2, b1, b2], 1)
+
+
+def closest_on_surface(V, F, Q):
+    """Where the points Q (n, 3) land on the triangle list (V, F), on the host: (closest points (n, 3),
+    triangle (n,), barycentric weights (n, 3)). Every triangle is tested (geom_report's Ericson
+    test); among equally close ones the lowest index wins. For scene builders: capi.closest_on_triangles
+    answers the same question on the device."""
+    from .geom_report import closest_on_triangles
+    V, F, Q = np.asarray(V, np.float64), np.asarray(F, np.int64).reshape(-1, 3), np.asarray(Q, np.float64).reshape(-1, 3)
+    A, B, C = V[F[:, 0]], V[F[:, 1]], V[F[:, 2]]
+    c, tri = np.zeros_like(Q), np.zeros(len(Q), np.int32)
+    for i, q in enumerate(Q):
+        cl = closest_on_triangles(np.broadcast_to(q, A.shape).copy(), A, B, C)
+        t = int(np.argmin(((cl - q) ** 2).sum(1)))
+        c[i], tri[i] = cl[t], t
+    return c, tri, tri_barycentric(A[tri], B[tri], C[tri], c)
+
+
+def sewn_panels_offset(n=4, *, gap=0.04, shift=0.37, inset=0.3, stitches=7, k=20.0, bend=None, size=0.5, iters=30, aa_m=6,
+                       accel=1, n_steps=3) -> Scene:
+    """Demo of a seam between panels whose nodes do not line up: two tri_grid(n, n) cloth panels of
+    side `size` side by side in the x-z plane, `gap` apart, the second slid along the seam by
+    `shift` cells, so that no node of one faces a node of the other. `stitches` zero-length
+    triangle-triangle ties (na = nb = 3) of stiffness k sew them: stitch i joins the point `inset`
+    cells inside the first panel's seam edge to the point as far inside the second's, at the same
+    height along the stretch of the seam that both panels cover; each point's triangle and weights
+    come from closest_on_surface. cloth()'s membrane on both; the far edge of the first panel is
+    held by its two corners."""
+    v, t = tri_grid(n, n, size)
+    nv, h = len(v), size / n
+    x = np.concatenate([v, v + np.array([size + gap, 0.0, shift * h])])
+    tris = np.concatenate([t, t + nv]).astype(np.int32)
+    zs = np.linspace(shift * h + 0.11 * h, size - 0.13 * h, stitches)
+    pa = np.stack([np.full(stitches, size - inset * h), np.zeros(stitches), zs], 1)
+    pb = np.stack([np.full(stitches, size + gap + inset * h), np.zeros(stitches), zs], 1)
+    _, ta, wa = closest_on_surface(x, tris[:len(t)], pa)
+    _, tb, wb = closest_on_surface(x, tris[len(t):], pb)
+    pins = np.array([0, n * (n + 1)], np.int32)
+    return Scene(x=x, masses=tri_masses(x, tris, 1.0), groups=[ElementGroup(TRI, LINEAR, 50.0, 0.1, tris, 0.95, 1.05)],
+                 pin_idx=pins, pin_pts=x[pins].copy(), pin_vel=np.zeros((2, 3)), variant=VARIANT_H, iters=iters, aa_m=aa_m,
+                 accel=accel, n_steps=n_steps, name="sewn_panels_offset",
+                 bending=None if bend is None else [(tris, float(bend), True)],
+                 ties=[(tris[:len(t)][ta], wa, tris[len(t):][tb], wb, float(k), np.zeros(stitches), SPRING)])
+
+
+def patch_on_block(cells=(2, 2, 2), cell=0.2, *, n=4, lift=0.03, k=200.0, mode=SPRING, rest=None, E=5e4, nu=0.3, floor=True,
+                   friction=0.5, drop=0.0, iters=30, aa_m=6, accel=1, n_steps=4) -> Scene:
+    """Demo of sewing a patch onto a body: a tet block (kuhn_tet_blocks, linear) and a tri_grid(n, n)
+    cloth patch, 0.7 of the block's top face wide, `lift` above it. Every rim node of the patch is
+    tied (node-triangle, na = 3, nb = 1, stiffness k, `mode`) to the point of the block's boundary
+    triangles it lies over -- closest_on_surface on the block's faces; rest = None: the distance at
+    the start. The patch shares no node with the block. floor: the block stands `drop` above a
+    FLOOR at y = 0 (obstacle row 0, Coulomb coefficient `friction`, contacts recorded), its bottom
+    nodes collision-checked. Block nodes come first, then the patch's."""
+    bv, bt = kuhn_tet_blocks(*cells)
+    bv = bv * float(cell) + np.array([0.0, drop, 0.0])
+    nb = len(bv)
+    faces = tet_boundary_faces(bv, bt)
+    lo, hi = bv.min(0), bv.max(0)
+    side = 0.7 * min(hi[0] - lo[0], hi[2] - lo[2])
+    pv, pt = tri_grid(n, n, side)
+    # off the block's own lattice lines, so that no rim node lies over an edge of a face
+    pv = pv + np.array([0.5 * (lo[0] + hi[0]) - 0.5 * side + 0.013 * cell, hi[1] + lift, 0.5 * (lo[2] + hi[2]) - 0.5 * side + 0.007 * cell])
+    x = np.concatenate([bv, pv])
+    g = np.arange((n + 1) * (n + 1)).reshape(n + 1, n + 1)
+    rim = np.unique(np.concatenate([g[0], g[-1], g[:, 0], g[:, -1]])).astype(np.int32)
+    _, tri, w = closest_on_surface(bv, faces, pv[rim])
+    ptris = (pt + nb).astype(np.int32)
+    sc = Scene(x=x, masses=np.concatenate([tet_masses(bv, bt, 1522.0), tri_masses(pv, pt, 1.0)]),
+               groups=[ElementGroup(TET, LINEAR, E, nu, bt), ElementGroup(TRI, LINEAR, 50.0, 0.1, ptris, 0.95, 1.05)],
+               pin_idx=np.zeros(0, np.int32), pin_pts=np.zeros((0, 3)), pin_vel=np.zeros((0, 3)), variant=VARIANT_H,
+               iters=iters, aa_m=aa_m, accel=accel, n_steps=n_steps, name="patch_on_block",
+               ties=[(faces[tri].astype(np.int32), w, (rim + nb).reshape(-1, 1).astype(np.int32), np.ones((len(rim), 1)),
+                      float(k), rest, int(mode))])
+    if floor:
+        sc.obstacles = [(OBS_FLOOR, (0.0,))]
+        sc.collision_idx = np.nonzero(bv[:, 1] < lo[1] + 1e-3 * cell)[0].astype(np.int32)
+        sc.obstacle_friction = [float(friction)]
+        sc.record_contacts = True
+    return sc
 
 
 def cantilever(cx=20, cy=4, cz=5, material=NEOHOOKEAN, *, variant=VARIANT_X, aa_m=6, iters=50,

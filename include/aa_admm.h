@@ -153,6 +153,43 @@ int aa_elastic_add_bending(aa_elastic h, const double* verts3, const int* tris3,
 enum { AA_SPRING = 0, AA_SPRING_TETHER = 1, AA_SPRING_STRUT = 2, AA_SPRING_HARD = 4 };
 int aa_elastic_add_springs(aa_elastic h, const double* verts3, const int* pairs2, int n_springs, int mode,
                            const double* k /* [n] */, const double* rest /* [n] or NULL */, int vertex_offset);
+/* Ties: springs between barycentric anchors (no counterpart in the reference). Tie e joins anchor
+ * A = sum_i a_i x_{A_i}, A_i = nodes_a[na e + i], a_i = w_a[na e + i], to anchor B = sum_j b_j x_{B_j}
+ * alike (node ids + vertex_offset): a node (1), a point on an edge (2), in a triangle (3) or in a tet
+ * (4), with 1 <= na, nb <= 4 and 3 <= na + nb <= 6. Its reduction row over the vertices (A_0 ..
+ * A_{na-1}, B_0 .. B_{nb-1}) is (-a_0 .. -a_{na-1}, +b_0 .. +b_{nb-1}), so z = p_B - p_A in R^3:
+ * na + nb vertices, one column, formed as the sum over the vertices in that order, left to right
+ * from 0, each term one fused multiply-add. The row sums to zero: a tie is an internal force. Rest
+ * length L = rest[e] >= 0, stiffness k[e] > 0, ADMM weight sqrt(k), one mode per call (one group per
+ * call); k, rest, mode and the prox are those of aa_elastic_add_springs, every mode included.
+ * rest == NULL: L = |p_B - p_A| at verts3, each anchor coordinate summed left to right from its
+ * first term, p = ((w_0 x_0 + w_1 x_1) + w_2 x_2) + w_3 x_3, d = p_B - p_A,
+ * L = sqrt((d0 d0 + d1 d1) + d2 d2), nothing contracted.
+ * Weights: finite, each side |sum w - 1| <= 1e-12, used as given (no renormalisation); a weight
+ * outside [0, 1] (an extrapolated anchor) or equal to zero is allowed. No node may appear twice in
+ * one tie, within an anchor or across the two. The anchors are fixed: they do not slide.
+ * Before initialize only (AA_ERR_STATE after). AA_ERR_ARG naming the first offending tie: an index
+ * out of range, a node twice, a weight not finite, a side not summing to 1, k not finite or not > 0,
+ * rest negative or not finite; also an unknown mode, na or nb outside 1..4, na + nb = 2 (use
+ * aa_elastic_add_springs), na + nb = 7 or 8 (triangle-tet, tet-tet: not provided), a null array with
+ * n_ties > 0, rest == NULL together with verts3 == NULL. A refused call changes nothing. initialize
+ * refuses a solver with ties in AA_VARIANT_Z and one partitioned over more than one rank. */
+int aa_elastic_add_ties(aa_elastic h, const double* verts3, int na, const int* nodes_a /* [n][na] */,
+                        const double* w_a /* [n][na] */, int nb, const int* nodes_b /* [n][nb] */,
+                        const double* w_b /* [n][nb] */, int n_ties, int mode, const double* k /* [n] */,
+                        const double* rest /* [n] or NULL */, int vertex_offset);
+/* Where on a triangle list does a point land (to find a tie's anchor)? For each of the n queries
+ * q3: the closest point of the surface, the caller's index of the triangle it lies on and its
+ * barycentric weights on that triangle's corners (Cramer's rule on the edge Gram matrix; (1, 0, 0)
+ * for a triangle whose Gram determinant is not > 0). Any triangle list: open and non-manifold ones
+ * are fine, no orientation is needed. The host builds a BVH; one kernel, one lane per query, runs the
+ * exact closest-point walk from a cold start, so the closest point is the exact minimum over all
+ * triangles; among triangles at the same distance the walk's first found wins (the leaf its greedy
+ * descent reaches, then depth-first order, strictly smaller distances replacing). AA_ERR_ARG for a
+ * non-finite coordinate (vertex or query), an index out of range, a zero-area triangle, an empty
+ * list. Not the mesh-obstacle path: nothing is added to a solver. closest3, tri or bary3 may be NULL. */
+int aa_closest_on_triangles(aa_ctx ctx, const double* verts3, int n_verts, const int* tris3, int n_tris,
+                            const double* q3, int n, double* closest3, int* tri, double* bary3);
 /* Solver::set_pins(inds, points): points3 == NULL pins in place (Solver.cpp:280-315). */
 int aa_elastic_set_pins(aa_elastic h, const int* inds, const double* points3, int n_pins);
 

@@ -58,7 +58,7 @@ public:
 class EnergyTerm {
 public:
     virtual ~EnergyTerm() {}
-    int kind = 0, material = AA_LINEAR;   // kind 0 tet, 1 tri, 3 bending hinges (BendingEnergyTerm), 4 springs (SpringEnergyTerm)
+    int kind = 0, material = AA_LINEAR;   // kind 0 tet, 1 tri, 3 bending hinges (BendingEnergyTerm), 4 springs (SpringEnergyTerm), 5 ties (TieEnergyTerm)
     Lame lame;
     std::vector<Lame> lames;     // per-element materials ([count]); empty: `lame` for every element
     std::vector<double> verts;   // rest shape (as given to create_*_from_mesh)
@@ -170,6 +170,44 @@ inline void create_springs(std::vector<std::shared_ptr<EnergyTerm>>& energyterms
         e->has_verts = true;
     }
     e->inds.assign(pairs, pairs + 2 * (size_t)n);
+    e->count = n;
+    e->vertex_offset = vertex_offset;
+    energyterms.push_back(e);
+}
+
+// Ties (aa_elastic_add_ties): n springs between barycentric anchors, anchor A of tie e the nodes
+// nodes_a[na e ..] with the weights w_a[na e ..], anchor B alike over nb nodes; stiffness k[e] and rest
+// length rest[e]; rest null takes the anchors' distance in verts (verts may be null when rest is
+// given). mode as for create_springs.
+class TieEnergyTerm : public EnergyTerm {
+public:
+    int na = 0, nb = 0;
+    std::vector<int> nodes_a, nodes_b;
+    std::vector<double> w_a, w_b, k, rest;   // rest empty: lengths from verts
+    int mode = AA_SPRING;
+    bool has_verts = false;
+};
+template <typename IN_SCALAR>
+inline void create_ties(std::vector<std::shared_ptr<EnergyTerm>>& energyterms, const IN_SCALAR* verts, int na, const int* nodes_a,
+                        const double* w_a, int nb, const int* nodes_b, const double* w_b, int n, const double* k,
+                        const double* rest, int mode, const int vertex_offset) {
+    auto e = std::make_shared<TieEnergyTerm>();
+    e->kind = 5;
+    e->mode = mode;
+    e->na = na; e->nb = nb;
+    e->nodes_a.assign(nodes_a, nodes_a + (size_t)na * n);
+    e->nodes_b.assign(nodes_b, nodes_b + (size_t)nb * n);
+    e->w_a.assign(w_a, w_a + (size_t)na * n);
+    e->w_b.assign(w_b, w_b + (size_t)nb * n);
+    e->k.assign(k, k + n);
+    if (rest) e->rest.assign(rest, rest + n);
+    if (verts) {
+        int nv = 0;
+        for (int i : e->nodes_a) nv = std::max(nv, i + 1);
+        for (int i : e->nodes_b) nv = std::max(nv, i + 1);
+        e->verts.assign(verts, verts + 3 * (size_t)nv);
+        e->has_verts = true;
+    }
     e->count = n;
     e->vertex_offset = vertex_offset;
     energyterms.push_back(e);
@@ -473,6 +511,10 @@ public:
                 } else if (const SpringEnergyTerm* sp = dynamic_cast<const SpringEnergyTerm*>(e.get())) {
                     rc = aa_elastic_add_springs(h_, sp->has_verts ? sp->verts.data() : nullptr, sp->inds.data(), sp->count, sp->mode,
                                                 sp->k.data(), sp->rest.empty() ? nullptr : sp->rest.data(), sp->vertex_offset);
+                } else if (const TieEnergyTerm* ti = dynamic_cast<const TieEnergyTerm*>(e.get())) {
+                    rc = aa_elastic_add_ties(h_, ti->has_verts ? ti->verts.data() : nullptr, ti->na, ti->nodes_a.data(), ti->w_a.data(),
+                                             ti->nb, ti->nodes_b.data(), ti->w_b.data(), ti->count, ti->mode, ti->k.data(),
+                                             ti->rest.empty() ? nullptr : ti->rest.data(), ti->vertex_offset);
                 } else if (!e->lames.empty()) {   // per-element materials: the _var calls
                     std::vector<aa_lame> ls;
                     for (auto& le : e->lames) ls.push_back(le.c());
