@@ -151,7 +151,7 @@ int aa_elastic_add_tets(aa_elastic h, const double* verts3, const int* tets4, in
                         int vertex_offset) {
     return guarded([&] {
         NEED(h && lame, "null argument");
-        h->s->add_elements(0, material, verts3, tets4, n, *lame, vertex_offset);
+        h->s->add_elements(aa::kTet, material, verts3, tets4, n, *lame, vertex_offset);
     });
 }
 
@@ -159,7 +159,7 @@ int aa_elastic_add_tris(aa_elastic h, const double* verts3, const int* tris3, in
                         int vertex_offset) {
     return guarded([&] {
         NEED(h && lame, "null argument");
-        h->s->add_elements(1, AA_LINEAR, verts3, tris3, n, *lame, vertex_offset);
+        h->s->add_elements(aa::kTri, AA_LINEAR, verts3, tris3, n, *lame, vertex_offset);
     });
 }
 
@@ -168,7 +168,7 @@ int aa_elastic_add_tets_var(aa_elastic h, const double* verts3, const int* tets4
     return guarded([&] {
         NEED(h, "null handle");
         NEED(lame_per_tet || n <= 0, "add_tets_var: null material array");
-        h->s->add_elements(0, material, verts3, tets4, n, aa_lame{}, vertex_offset, n > 0 ? lame_per_tet : nullptr);
+        h->s->add_elements(aa::kTet, material, verts3, tets4, n, aa_lame{}, vertex_offset, n > 0 ? lame_per_tet : nullptr);
     });
 }
 
@@ -177,7 +177,7 @@ int aa_elastic_add_tris_var(aa_elastic h, const double* verts3, const int* tris3
     return guarded([&] {
         NEED(h, "null handle");
         NEED(lame_per_tri || n <= 0, "add_tris_var: null material array");
-        h->s->add_elements(1, AA_LINEAR, verts3, tris3, n, aa_lame{}, vertex_offset, n > 0 ? lame_per_tri : nullptr);
+        h->s->add_elements(aa::kTri, AA_LINEAR, verts3, tris3, n, aa_lame{}, vertex_offset, n > 0 ? lame_per_tri : nullptr);
     });
 }
 

@@ -48,7 +48,7 @@ struct ContactFeatDev {
     int* tri;
     double* b;
 };
-// g: a collision group (kind 2). xold: the step's start state (all nodes); xsrc: the free nodes'
+// g: a collision group (kCollision). xold: the step's start state (all nodes); xsrc: the free nodes'
 // new positions, the buffer the finalize pass reads (moved in place); xfull: the pinned nodes'.
 // rec_off: the group's first record.
 void launch_contact_friction(const GroupDev& g, const double* xold, double* xsrc, const double* xfull, const double* u,

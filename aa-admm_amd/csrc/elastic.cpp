@@ -55,7 +55,7 @@ int ElasticSolver::add_nodes(const double* x3, const double* m3, int n) {
 // per_element: the reference's one EnergyTerm per element, each with its own Lame (TetEnergyTerm.hpp:36-51,
 // TriEnergyTerm.hpp:33-47) -- n create_*_from_mesh calls of one element each, in element order, as one
 // group. The scalar calls' checks apply per element; the message names the first offending element.
-void ElasticSolver::add_elements(int kind, int material, const double* verts3, const int* idx, int count,
+void ElasticSolver::add_elements(ElemKind kind, int material, const double* verts3, const int* idx, int count,
                                  const aa_lame& lame, int vertex_offset, const aa_lame* per) {
     if (count < 0 || (count > 0 && (!verts3 || !idx))) throw Error(ERR_ARG, "add_elements: bad input");
     if (initialized_) throw Error(ERR_STATE, "adding energy terms after initialize is not supported");
@@ -66,20 +66,20 @@ void ElasticSolver::add_elements(int kind, int material, const double* verts3, c
     auto check_lame = [&](const aa_lame& l, int t) {
         if (per && (!std::isfinite(l.mu) || !std::isfinite(l.lambda)))
             throw Error(ERR_ARG, at("add_elements: mu and lambda must be finite", t));
-        if (kind != 1) return;
+        if (kind != kTri) return;
         if (l.limit_min > 1.0) throw Error(ERR_ARG, at("**TriEnergyTerm Error: Strain limit min should be -inf to 1", t));
         if (l.limit_max < 1.0) throw Error(ERR_ARG, at("**TriEnergyTerm Error: Strain limit max should be 1 to inf", t));
     };
-    if (kind == 1) material = AA_LINEAR;
+    if (kind == kTri) material = AA_LINEAR;
     else if (material < 0 || material > 2) throw Error(ERR_ARG, "add_tets: unknown material");
     if (!per) check_lame(lame, 0);
     HostGroup g;
     g.kind = kind; g.material = material; g.lame = per ? aa_lame{} : lame;
-    g.nv = kind == 0 ? 4 : 3; g.ncol = g.nv - 1;
+    g.nv = kind == kTet ? 4 : 3; g.ncol = kind_ncol(kind, g.nv);
     double k = lame.lambda + (2.0 / 3.0) * lame.mu;
     if (per) {
         g.mu_e.resize(count); g.lambda_e.resize(count); g.k_e.resize(count);
-        if (kind == 1) { g.lmin_e.resize(count); g.lmax_e.resize(count); }
+        if (kind == kTri) { g.lmin_e.resize(count); g.lmax_e.resize(count); }
     }
     g.idx.resize((size_t)count * g.nv);
     g.G.resize((size_t)count * g.ncol * g.nv);
@@ -89,7 +89,7 @@ void ElasticSolver::add_elements(int kind, int material, const double* verts3, c
             check_lame(per[t], t);
             g.mu_e[t] = per[t].mu; g.lambda_e[t] = per[t].lambda;
             g.k_e[t] = k = per[t].lambda + (2.0 / 3.0) * per[t].mu;
-            if (kind == 1) { g.lmin_e[t] = per[t].limit_min; g.lmax_e[t] = per[t].limit_max; }
+            if (kind == kTri) { g.lmin_e[t] = per[t].limit_min; g.lmax_e[t] = per[t].limit_max; }
         }
         const double* P[4];
         for (int a = 0; a < g.nv; ++a) {
@@ -100,7 +100,7 @@ void ElasticSolver::add_elements(int kind, int material, const double* verts3, c
         }
         double* G = &g.G[(size_t)t * g.ncol * g.nv];
         double vol;
-        if (kind == 0) {
+        if (kind == kTet) {
             double B[9];
             for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) B[r * 3 + c] = P[c + 1][r] - P[0][r];
             double cof[9];
@@ -146,77 +146,60 @@ void ElasticSolver::add_elements(int kind, int material, const double* verts3, c
     hgroups_.push_back(std::move(g));
 }
 
-// Bending hinges of a triangle list (bending.hpp): one group of kind 3, four vertices and the one
-// column z = K x per hinge, w = sqrt(kappa); the rest length r rides in `vol`.
+// The tail the one-column builders share. idx is in the caller's numbering: an index is in range when
+// its node exists, idx + vertex_offset in [0, num_nodes); the builders refused the upper end already.
+void ElasticSolver::add_one_col_group(ElemKind kind, int material, int nv, const std::vector<int>& idx,
+                                      std::vector<double>&& G, std::vector<double>&& vol, std::vector<double>&& w,
+                                      int vertex_offset, const char* who) {
+    for (size_t i = 0; i < idx.size(); ++i)
+        if (idx[i] + vertex_offset < 0)
+            throw Error(ERR_ARG, std::string(who) + ": " + kind_traits(kind).term + " " + std::to_string(i / nv) +
+                                     " has a node index out of range");
+    HostGroup g;
+    g.kind = kind; g.material = material; g.lame = aa_lame{};
+    g.nv = nv; g.ncol = kind_ncol(kind, nv);
+    g.idx.resize(idx.size());
+    for (size_t i = 0; i < idx.size(); ++i) g.idx[i] = idx[i] + vertex_offset;
+    g.G = std::move(G); g.vol = std::move(vol); g.w = std::move(w);
+    hgroups_.push_back(std::move(g));
+}
+
+// Bending hinges of a triangle list (bending.hpp): one kHinge group, w = sqrt(kappa).
 int ElasticSolver::add_bending(const double* verts3, const int* tris3, int n_tris, double k_bend, bool flat_rest,
                                int vertex_offset) {
     if (initialized_) throw Error(ERR_STATE, "add_bending: adding energy terms after initialize is not supported");
-    // the rest shape is verts3[tris3], the nodes tris3 + vertex_offset: an index is in range when its node exists
-    const HingeSet H = build_hinges(verts3, num_nodes() - vertex_offset, tris3, n_tris, k_bend, flat_rest);
+    // the rest shape is verts3[tris3], the nodes tris3 + vertex_offset
+    HingeSet H = build_hinges(verts3, num_nodes() - vertex_offset, tris3, n_tris, k_bend, flat_rest);
     const int count = H.count();
+    // (every triangle's indices, not only the hinges': the message names the triangle)
     for (int t = 0; t < n_tris; ++t)
         for (int a = 0; a < 3; ++a)
             if (tris3[3 * (size_t)t + a] + vertex_offset < 0)
                 throw Error(ERR_ARG, "add_bending: triangle " + std::to_string(t) + " has a vertex index out of range");
-    HostGroup g;
-    g.kind = 3; g.material = AA_LINEAR; g.lame = aa_lame{};
-    g.nv = 4; g.ncol = 1;
-    g.idx.resize((size_t)count * 4);
-    for (size_t i = 0; i < g.idx.size(); ++i) g.idx[i] = H.idx[i] + vertex_offset;
-    g.G = H.K;
-    g.vol = H.r;
-    g.w.resize(count);
+    std::vector<double> w(count);
     for (int e = 0; e < count; ++e) {
-        g.w[e] = std::sqrt(H.kappa[e]);
-        if (!(g.w[e] > 0.0) || !std::isfinite(g.w[e]))
+        w[e] = std::sqrt(H.kappa[e]);
+        if (!(w[e] > 0.0) || !std::isfinite(w[e]))
             throw Error(ERR_NUMERIC, "add_bending: hinge " + std::to_string(e) + " has a weight that is not positive and finite");
     }
-    hgroups_.push_back(std::move(g));
+    add_one_col_group(kHinge, AA_LINEAR, 4, H.idx, std::move(H.K), std::move(H.r), std::move(w), vertex_offset, "add_bending");
     return count;
 }
 
-// Springs (springs.hpp): one group of kind 4, two vertices and the one column z = x_b - x_a per
-// spring, w = sqrt(k); the rest length L rides in `vol`, the mode in `material`.
+// Springs (springs.hpp): one kSpring group, w = sqrt(k).
 void ElasticSolver::add_springs(const double* verts3, const int* pairs2, int n_springs, int mode, const double* k,
                                 const double* rest, int vertex_offset) {
     if (initialized_) throw Error(ERR_STATE, "add_springs: adding energy terms after initialize is not supported");
-    // an index is in range when its node exists: pairs2 + vertex_offset in [0, num_nodes)
-    const SpringSet S = build_springs(verts3, num_nodes() - vertex_offset, pairs2, n_springs, mode, k, rest);
-    for (int e = 0; e < n_springs; ++e)
-        for (int a = 0; a < 2; ++a)
-            if (pairs2[2 * (size_t)e + a] + vertex_offset < 0)
-                throw Error(ERR_ARG, "add_springs: spring " + std::to_string(e) + " has a node index out of range");
-    HostGroup g;
-    g.kind = 4; g.material = mode; g.lame = aa_lame{};
-    g.nv = 2; g.ncol = 1;
-    g.idx.resize(S.idx.size());
-    for (size_t i = 0; i < g.idx.size(); ++i) g.idx[i] = S.idx[i] + vertex_offset;
-    g.G = S.G;
-    g.vol = S.L;
-    g.w = S.w;
-    hgroups_.push_back(std::move(g));
+    SpringSet S = build_springs(verts3, num_nodes() - vertex_offset, pairs2, n_springs, mode, k, rest);
+    add_one_col_group(kSpring, mode, 2, S.idx, std::move(S.G), std::move(S.L), std::move(S.w), vertex_offset, "add_springs");
 }
 
-// Ties (ties.hpp): one group of kind 5, na + nb vertices and the one column z = p_B - p_A per tie,
-// w = sqrt(k); the rest length L rides in `vol`, the mode in `material`.
+// Ties (ties.hpp): one kTie group of na + nb vertices, w = sqrt(k).
 void ElasticSolver::add_ties(const double* verts3, int na, const int* nodes_a, const double* w_a, int nb, const int* nodes_b,
                              const double* w_b, int n_ties, int mode, const double* k, const double* rest, int vertex_offset) {
     if (initialized_) throw Error(ERR_STATE, "add_ties: adding energy terms after initialize is not supported");
-    // an index is in range when its node exists: node + vertex_offset in [0, num_nodes)
-    const TieSet S = build_ties(verts3, num_nodes() - vertex_offset, na, nodes_a, w_a, nb, nodes_b, w_b, n_ties, mode, k, rest);
-    for (int e = 0; e < n_ties; ++e)
-        for (int a = 0; a < S.nv; ++a)
-            if (S.idx[(size_t)S.nv * e + a] + vertex_offset < 0)
-                throw Error(ERR_ARG, "add_ties: tie " + std::to_string(e) + " has a node index out of range");
-    HostGroup g;
-    g.kind = 5; g.material = mode; g.lame = aa_lame{};
-    g.nv = S.nv; g.ncol = 1;
-    g.idx.resize(S.idx.size());
-    for (size_t i = 0; i < g.idx.size(); ++i) g.idx[i] = S.idx[i] + vertex_offset;
-    g.G = S.G;
-    g.vol = S.L;
-    g.w = S.w;
-    hgroups_.push_back(std::move(g));
+    TieSet S = build_ties(verts3, num_nodes() - vertex_offset, na, nodes_a, w_a, nb, nodes_b, w_b, n_ties, mode, k, rest);
+    add_one_col_group(kTie, mode, S.nv, S.idx, std::move(S.G), std::move(S.L), std::move(S.w), vertex_offset, "add_ties");
 }
 
 void ElasticSolver::HostGroup::append_element(const HostGroup& from, size_t t) {
@@ -577,30 +560,25 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
         throw Error(ERR_ARG, "initialize: obstacle friction or contact recording is on and the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (a rank holds only its part of the collision terms; friction needs one rank)");
     if (comm_ && comm_->size() > 1 && any_bound())
         throw Error(ERR_ARG, "initialize: a mesh obstacle is bound to solver nodes and the solver is partitioned over " + std::to_string(comm_->size()) + " ranks (bound obstacles need one rank)");
-    const bool bending = std::any_of(hgroups_.begin(), hgroups_.end(), [](const HostGroup& g) { return g.kind == 3; });
-    if (bending && st_.variant == AA_VARIANT_Z)
-        throw Error(ERR_ARG, "initialize: bending hinges exist in the (u,x) variant only (the z variant's gradient step has no hinge term)");
-    if (bending && comm_ && comm_->size() > 1)
-        throw Error(ERR_ARG, "initialize: the solver has bending hinges and is partitioned over " + std::to_string(comm_->size()) + " ranks (bending needs one rank)");
-    const bool springs = std::any_of(hgroups_.begin(), hgroups_.end(), [](const HostGroup& g) { return g.kind == 4; });
-    if (springs && st_.variant == AA_VARIANT_Z)
-        throw Error(ERR_ARG, "initialize: springs exist in the (u,x) variant only (the z variant's gradient step has no spring term)");
-    if (springs && comm_ && comm_->size() > 1)
-        throw Error(ERR_ARG, "initialize: the solver has springs and is partitioned over " + std::to_string(comm_->size()) + " ranks (springs need one rank)");
-    const bool ties = std::any_of(hgroups_.begin(), hgroups_.end(), [](const HostGroup& g) { return g.kind == 5; });
-    if (ties && st_.variant == AA_VARIANT_Z)
-        throw Error(ERR_ARG, "initialize: ties exist in the (u,x) variant only (the z variant's gradient step has no tie term)");
-    if (ties && comm_ && comm_->size() > 1)
-        throw Error(ERR_ARG, "initialize: the solver has ties and is partitioned over " + std::to_string(comm_->size()) + " ranks (ties need one rank)");
+    // the kinds the z variant and partitioned solvers do not take, in the order of the kinds
+    for (int k = 0; k < kNumKinds; ++k) {
+        const KindTraits kt = kind_traits((ElemKind)k);
+        if (kt.z_and_ranks || std::none_of(hgroups_.begin(), hgroups_.end(), [&](const HostGroup& g) { return g.kind == k; }))
+            continue;
+        if (st_.variant == AA_VARIANT_Z)
+            throw Error(ERR_ARG, std::string("initialize: ") + kt.noun + " exist in the (u,x) variant only (the z variant's gradient step has no " + kt.term + " term)");
+        if (comm_ && comm_->size() > 1)
+            throw Error(ERR_ARG, std::string("initialize: the solver has ") + kt.noun + " and is partitioned over " + std::to_string(comm_->size()) + " ranks (" + kt.needs + " one rank)");
+    }
     if (st_.variant == AA_VARIANT_Z && !coll_nodes_.empty())
         throw Error(ERR_ARG, "set_collisions: energy-based collisions exist in the (u,x) variant only (admm_anderson_hard_zxu)");
     // collision terms (Solver.cpp:386-392): after the other terms, one per node in node order;
     // Lame::soft_rubber (EnergyTerm.hpp:38), weight sqrt(2 k), volume 2 (CollisionEnergyTerm.hpp:63-70)
-    hgroups_.erase(std::remove_if(hgroups_.begin(), hgroups_.end(), [](const HostGroup& g) { return g.kind == 2; }),
+    hgroups_.erase(std::remove_if(hgroups_.begin(), hgroups_.end(), [](const HostGroup& g) { return g.kind == kCollision; }),
                    hgroups_.end());
     if (!coll_nodes_.empty()) {
         HostGroup g;
-        g.kind = 2; g.material = AA_LINEAR; g.nv = 1; g.ncol = 1;
+        g.kind = kCollision; g.material = AA_LINEAR; g.nv = 1; g.ncol = kind_ncol(kCollision, 1);
         const double E = 10000000.0, nu = 0.399;
         g.lame = aa_lame{};
         g.lame.mu = E / (2.0 * (1.0 + nu));
@@ -864,7 +842,7 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
                 dg.var.lmin = dg.lmin_e.p; dg.var.lmax = dg.lmax_e.p;
             }
         }
-        if (hg.kind == 2) {   // the obstacle table the collision prox reads (fixed address: graph-safe)
+        if (hg.kind == kCollision) {   // the obstacle table the collision prox reads (fixed address: graph-safe)
             if (!obs_dev_.p) obs_dev_.alloc(1 + (size_t)kObsStride * kMaxObstacles);
             d.obs = obs_dev_.p;
         } else {
@@ -1019,8 +997,8 @@ void ElasticSolver::initialize(const aa_settings& s_in) {
     for (auto& g : groups_) {
         const double per = 4.0 * g.d.nv + 8.0 * g.d.ncol * g.d.nv + 8.0;
         lz += g.d.count * (per + 2 * 8.0 * g.d.dim + 28.0 * g.d.nv);   // u in, z out, slot positions + slots out
-        if (g.var) lz += g.d.count * (g.d.kind == 1 ? 16.0 : g.d.mat != 0 ? 24.0 : 0.0);   // per-element materials
-        if (g.d.kind >= 3 && g.d.kind <= 5) lz += g.d.count * 8.0;   // a hinge's, a spring's or a tie's rest length
+        if (g.var) lz += g.d.count * (g.d.kind == kTri ? 16.0 : g.d.mat != 0 ? 24.0 : 0.0);   // per-element materials
+        if (kind_traits(g.d.kind).rest_in_vol) lz += g.d.count * 8.0;   // a hinge's, a spring's or a tie's rest length
         rs += g.d.count * (per + 3 * 8.0 * g.d.dim);
     }
     kstats_["local_z"].bytes = lz + 24.0 * n;
@@ -1504,7 +1482,7 @@ void ElasticSolver::friction_enqueue(bool accel) {
         return;
     }
     fr_ran_ = true;
-    for (auto& g : groups_) if (g.d.kind == 2) fr_count_ += g.d.count;
+    for (auto& g : groups_) if (g.d.kind == kCollision) fr_count_ += g.d.count;
     const int nobs = (int)obstacles_.size(), nmesh = (int)meshes_.size();
     if (fr_count_ > 0) {
         if (!fr_prev_valid_) { obs_prev_ = obstacles_; mesh_rows_prev_ = mesh_rows_; }
@@ -1564,7 +1542,7 @@ void ElasticSolver::friction_enqueue(bool accel) {
         AA_HIP(hipEventRecord(fr_ev0_, s()));   // kernel_stats("friction"): the pass's device time
         int off = 0;
         for (auto& g : groups_) {
-            if (g.d.kind != 2) continue;
+            if (g.d.kind != kCollision) continue;
             if (carry)
                 launch_contact_friction_carry(g.d, xs_.p, xsrc, xfull_.p, u, mass_.p, nf_, st_.penalty, st_.timestep_s,
                                               mesh_table(g.d), T, rec, off, fr_carry_.p, feat, s());
@@ -1608,7 +1586,7 @@ int ElasticSolver::contacts(int cap, int* node, int* obstacle, double* point3, d
     int k = 0;
     size_t e = 0;
     for (auto& g : groups_) {
-        if (g.d.kind != 2) continue;
+        if (g.d.kind != kCollision) continue;
         std::vector<int> idx((size_t)g.d.count);
         AA_HIP(hipMemcpy(idx.data(), g.idx.p, idx.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int t = 0; t < g.d.count; ++t, ++e) {

@@ -73,14 +73,14 @@ public:
 
     int add_nodes(const double* x3, const double* m3, int n);
     // per_element given: [count] Lame parameters, one per element (aa_elastic_add_*_var); `lame` is then unused
-    void add_elements(int kind, int material, const double* verts3, const int* idx, int count, const aa_lame& lame,
+    void add_elements(ElemKind kind, int material, const double* verts3, const int* idx, int count, const aa_lame& lame,
                       int vertex_offset, const aa_lame* per_element = nullptr);
     // bending hinges on the interior edges of a triangle list (bending.hpp); returns their count
     int add_bending(const double* verts3, const int* tris3, int n_tris, double k_bend, bool flat_rest, int vertex_offset);
-    // two-node springs (springs.hpp): one group of kind 4 per call; node ids pairs2 + vertex_offset
+    // two-node springs (springs.hpp): one kSpring group per call; node ids pairs2 + vertex_offset
     void add_springs(const double* verts3, const int* pairs2, int n_springs, int mode, const double* k, const double* rest,
                      int vertex_offset);
-    // ties between barycentric anchors (ties.hpp): one group of kind 5 per call; node ids + vertex_offset
+    // ties between barycentric anchors (ties.hpp): one kTie group per call; node ids + vertex_offset
     void add_ties(const double* verts3, int na, const int* nodes_a, const double* w_a, int nb, const int* nodes_b,
                   const double* w_b, int n_ties, int mode, const double* k, const double* rest, int vertex_offset);
     void set_pins(const int* inds, const double* pts3, int n);
@@ -162,7 +162,8 @@ public:
 
 private:
     struct HostGroup {
-        int kind, material, nv, ncol;   // kind 3 (bending hinge): G holds K, vol the rest length r; kind 4 (spring): G = (-1, +1), vol = L, material = the mode; kind 5 (tie): G = (-a, +b), nv = na + nb, else as a spring
+        ElemKind kind;              // what G, vol and material hold for it: kind_traits (elastic_kernels.hpp)
+        int material, nv, ncol;
         aa_lame lame;
         std::vector<int> idx;       // [count][nv] global node ids
         std::vector<double> G;      // [count][ncol][nv]
@@ -197,6 +198,10 @@ private:
     };
     std::vector<std::unique_ptr<Wind>> winds_;
     DevBuf<double> obs_dev_;
+    // the tail of add_bending / add_springs / add_ties: the caller-numbered idx checked and offset,
+    // G / vol / w moved into one new group; `who` is the caller's name in the message
+    void add_one_col_group(ElemKind kind, int material, int nv, const std::vector<int>& idx, std::vector<double>&& G,
+                           std::vector<double>&& vol, std::vector<double>&& w, int vertex_offset, const char* who);
     void upload_obstacles();
     // mesh obstacles: each one's BVH and pseudonormals, and the table of their device views the
     // mesh-aware collision prox indexes (kMaxMeshObstacles rows, allocated once: a fixed address,
@@ -213,7 +218,7 @@ private:
     void upload_mesh_exempt(int mesh_id);
     void refresh_bound_mesh(int mesh_id);   // host row lo / hi and host vertices from the device
     bool any_bound() const { for (auto& m : meshes_) if (m->bound) return true; return false; }
-    const MeshObsDev* mesh_table(const GroupDev& d) const { return d.kind == 2 && !meshes_.empty() ? mesh_dev_.p : nullptr; }
+    const MeshObsDev* mesh_table(const GroupDev& d) const { return d.kind == kCollision && !meshes_.empty() ? mesh_dev_.p : nullptr; }
     void build_wind(Wind& w);
     // friction: the coefficients, the obstacle state in force during the previous step (host
     // snapshots, uploaded before the pass; valid once the pass has run in the step before), the

@@ -7,6 +7,7 @@
 // comb < eps break) on the device so the whole ADMM loop is enqueued without host syncs.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.hpp"
 #include "device_lbfgs.hpp"
@@ -84,10 +85,10 @@ __device__ __forceinline__ bool gated(const Ctrl* c, int gate_reject) {
 }
 
 // F = P x_full, Cp = P_pinned x_pin  (EnergyTerm::update_z's D.block*x, Solver.cpp C_fix)
-template <int S>
+// (the gathers and write_slots take NV and NC; NC left out: a simplex's, as the tet queue kernels call them)
+template <int NV, int NC = ncol_of(NV)>
 __device__ __forceinline__ void gather_F(const GroupDev& g, int e, const double* __restrict__ xfull, int nf, double* F,
                                          double* Cp) {
-    constexpr int NV = shape_nv(S), NC = shape_nc(S);
 #pragma unroll
     for (int i = 0; i < 3 * NC; ++i) { F[i] = 0; Cp[i] = 0; }
 #pragma unroll
@@ -107,21 +108,19 @@ __device__ __forceinline__ void gather_F(const GroupDev& g, int e, const double*
 // Cp alone, for the callers that need only C_fix (the rhs slots after the gradient pass): a group without pinned nodes (g.pinned = 0, kernel-uniform) has Cp = 0 and loads
 // no position; otherwise gather_F's products (F unused). A per-node `if pinned` branch instead was
 // measured slower (the node id load then waits before anything else issues): C4 local_z 412 -> 430 us.
-template <int S>
+template <int NV, int NC = ncol_of(NV)>
 __device__ __forceinline__ void gather_Cp(const GroupDev& g, int e, const double* __restrict__ xfull, int nf, double* Cp) {
-    constexpr int NC = shape_nc(S);
     if (!g.pinned) {
 #pragma unroll
         for (int i = 0; i < 3 * NC; ++i) Cp[i] = 0;
         return;
     }
     double F[3 * NC];
-    gather_F<S>(g, e, xfull, nf, F, Cp);
+    gather_F<NV, NC>(g, e, xfull, nf, F, Cp);
 }
 
-template <int S>
+template <int NV, int NC = ncol_of(NV)>
 __device__ __forceinline__ void gather_P(const GroupDev& g, int e, const double* __restrict__ xfull, double* F) {
-    constexpr int NV = shape_nv(S), NC = shape_nc(S);
 #pragma unroll
     for (int i = 0; i < 3 * NC; ++i) F[i] = 0;
 #pragma unroll
@@ -161,10 +160,9 @@ __device__ __forceinline__ void write_slots_pre(const int* pos, const double* gk
         o[0] = f0; o[1] = f1; o[2] = f2;
     }
 }
-template <int S>
+template <int NV, int NC = ncol_of(NV)>
 __device__ __forceinline__ void write_slots(const GroupDev& g, int e, int nf, double w, const double* zz,
                                             const double* Cp, const double* uu, double* __restrict__ y) {
-    constexpr int NV = shape_nv(S), NC = shape_nc(S);
     double yc[3 * NC];
 #pragma unroll
     for (int i = 0; i < 3 * NC; ++i) yc[i] = w * (w * zz[i] - w * Cp[i] - uu[i]);
@@ -239,35 +237,34 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
     constexpr bool VAR = kVar<V...>;
     if (mode != LZ_INIT && gated(ctrl, mode == LZ_REDO)) return;
     __shared__ double sm[kBlock / 64];
+    constexpr ElemKind K = shape_kind(S);
     constexpr int NV = shape_nv(S), NC = shape_nc(S), D = 3 * NC;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     double part = 0;
     if (e < g.count) {
         double F[D], Cp[D], uu[D], vin[D], zz[D];
-        gather_F<S>(g, e, xfull, nf, F, Cp);
+        gather_F<NV, NC>(g, e, xfull, nf, F, Cp);
         const double w = g.w[e];
         double rest = 0.0;   // the hinge's r / the spring's or tie's L, with the other loads
-        if constexpr (S == kShapeHinge || S == kShapeSpring || shape_is_tie(S)) rest = g.vol[e];
+        if constexpr (kind_traits(K).rest_in_vol) rest = g.vol[e];
         load_u<D>(g, e, u, uu);
 #pragma unroll
         for (int i = 0; i < D; ++i) vin[i] = F[i] + uu[i] / w;
-        if constexpr (shape_is_tie(S)) {   // first: a tie has 3..6 vertices, none of the simplex branches is its
+        if constexpr (K == kSpring || K == kTie) {   // a tie is a spring between its two anchors
             dev::spring_prox(vin, rest, g.mat, zz);
-        } else if constexpr (NV == 1) {
+        } else if constexpr (K == kCollision) {
             // the (u,x) variant's candidate exactly as EnergyTerm::update_z forms it for an identity
             // row (EnergyTerm.hpp:166-178: z = W^-1 (W x + u - c), W^-1 stored as 1/w): the
             // contact decision is discrete, so the candidate is rounded like the reference's
             if (variant == 1) dev::collision_candidate(F, uu, w, vin);
             if constexpr (VAR) dev::collision_prox(vin, g.obs, zz, gvp..., g.idx[e]);   // the pack is the mesh table; + the node
             else dev::collision_prox(vin, g.obs, zz);
-        } else if constexpr (NV == 3) {
+        } else if constexpr (K == kTri) {
             if constexpr (VAR) dev::tri_prox(vin, zz, variant, var_of(gvp...).lmin[e], var_of(gvp...).lmax[e]);
             else dev::tri_prox(vin, zz, variant, g.lmin, g.lmax);
-        } else if constexpr (S == kShapeHinge) {
+        } else if constexpr (K == kHinge) {
             dev::hinge_prox(vin, rest, zz);
-        } else if constexpr (S == kShapeSpring) {
-            dev::spring_prox(vin, rest, g.mat, zz);
-        } else if constexpr (HYPER == 0) {
+        } else if constexpr (HYPER == 0) {   // kTet from here
             dev::tet_linear_prox(vin, zz);
         } else {
 #pragma unroll
@@ -287,7 +284,7 @@ __global__ __launch_bounds__(kBlock) void k_local_z(GroupDev g, const double* __
             part += r * r;
             z[g.zoff + (size_t)i * g.count + e] = zz[i];
         }
-        if (y) write_slots<S>(g, e, nf, w, zz, Cp, uu, y);
+        if (y) write_slots<NV, NC>(g, e, nf, w, zz, Cp, uu, y);
     }
     if (red) {
         const double s = block_sum(part, sm);
@@ -780,20 +777,21 @@ __global__ __launch_bounds__(kBlock, 2) void k_local_z_hq2(GroupDev g, const dou
 }
 
 // r = w(P x - z): prim2 += |r|^2, dual2 += |w P (x - x_last)|^2, u += r
-template <int S>
+// (k_resid_u, k_prim_z and k_init_z read a shape's NV and NC only: one instantiation per pair)
+template <int NV, int NC>
 __global__ __launch_bounds__(kBlock) void k_resid_u(GroupDev g, const double* __restrict__ xfull,
                                                     const double* __restrict__ xlast, const double* __restrict__ z,
                                                     double* __restrict__ u, int nf, Ctrl* ctrl, double* red_a,
                                                     double* red_b, int red_off) {
     if (gated(ctrl, 0)) return;
     __shared__ double sm[kBlock / 64];
-    constexpr int D = 3 * shape_nc(S);
+    constexpr int D = 3 * NC;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     double pa = 0, pb = 0;
     if (e < g.count) {
         double F[D], Fl[D];
-        gather_P<S>(g, e, xfull, F);
-        gather_P<S>(g, e, xlast, Fl);
+        gather_P<NV, NC>(g, e, xfull, F);
+        gather_P<NV, NC>(g, e, xlast, Fl);
         const double w = g.w[e];
 #pragma unroll
         for (int i = 0; i < D; ++i) {
@@ -821,9 +819,8 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
                                                     V... gvp) {
     constexpr bool VAR = kVar<V...>;
     if (gated(ctrl, redo)) return;
-    // (a hinge, a spring or a tie counts as a shape of its own below: NV is 0 for it, none of the simplex branches)
-    constexpr bool ONE_COL = S == kShapeHinge || S == kShapeSpring || shape_is_tie(S);
-    constexpr int NV = ONE_COL ? 0 : shape_nv(S), D = 3 * shape_nc(S);
+    constexpr ElemKind K = shape_kind(S);
+    constexpr int NV = shape_nv(S), NC = shape_nc(S), D = 3 * NC;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= g.count) return;
     // the gradient (mode 1) needs only z: it runs before the element's gathers, so its
@@ -831,9 +828,9 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
     double F[D], Cp[D], zz[D], uu[D];
     const double w = g.w[e];
     // the element volume with the other loads (loaded where it is used, it waited alone mid-gradient)
-    const double vol = (NV == 4 && mode == 1) ? g.vol[e] : 0.0;
+    const double vol = (K == kTet && mode == 1) ? g.vol[e] : 0.0;
     double mu = g.mu, lambda = g.lambda, k = g.k;
-    if constexpr (VAR && NV == 4) {
+    if constexpr (VAR && K == kTet) {
         const GroupVar& gv = var_of(gvp...);
         if (mode == 1) { mu = gv.mu[e]; lambda = gv.lambda[e]; k = gv.k[e]; }
     }
@@ -845,7 +842,7 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
     }
     if (mode == 1) {
         double gr[D];
-        if constexpr (NV == 3 || NV == 1 || ONE_COL) {
+        if constexpr (K != kTet) {
             // TriEnergyTerm::get_gradient / Collision::get_gradient throw in the reference; a hinge,
             // spring or tie group is refused in the Z variant (initialize), so mode 1 never reaches it
             if (ctrl) ctrl->fail = 2;
@@ -862,32 +859,32 @@ __global__ __launch_bounds__(kBlock) void k_u_and_y(GroupDev g, const double* __
         for (int i = 0; i < D; ++i) uu[i] = gr[i] / w;
     }
     if (mode == 0) {
-        gather_F<S>(g, e, xfull, nf, F, Cp);
+        gather_F<NV, NC>(g, e, xfull, nf, F, Cp);
 #pragma unroll
         for (int i = 0; i < D; ++i) uu[i] += w * F[i] - w * zz[i];
     } else {
-        gather_Cp<S>(g, e, xfull, nf, Cp);
+        gather_Cp<NV, NC>(g, e, xfull, nf, Cp);
     }
     if (mode != 2) {
 #pragma unroll
         for (int i = 0; i < D; ++i) u[g.zoff + (size_t)i * g.count + e] = uu[i];
     }
-    write_slots<S>(g, e, nf, w, zz, Cp, uu, y);
+    write_slots<NV, NC>(g, e, nf, w, zz, Cp, uu, y);
 }
 
-template <int S>
+template <int NV, int NC>
 __global__ __launch_bounds__(kBlock) void k_prim_z(GroupDev g, const double* __restrict__ xfull,
                                                    const double* __restrict__ z, const double* __restrict__ zref,
                                                    int nf, int redo, Ctrl* ctrl, double* red_a, double* red_b,
                                                    int red_off) {
     if (gated(ctrl, redo)) return;
     __shared__ double sm[kBlock / 64];
-    constexpr int D = 3 * shape_nc(S);
+    constexpr int D = 3 * NC;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     double pa = 0, pb = 0;
     if (e < g.count) {
         double F[D];
-        gather_P<S>(g, e, xfull, F);
+        gather_P<NV, NC>(g, e, xfull, F);
         const double w = g.w[e];
         double zi[D], zr[D];   // all loads first (a load under `if (zref)` waited per entry)
 #pragma unroll
@@ -926,13 +923,13 @@ __global__ __launch_bounds__(kBlock) void k_prim_sum(GroupDev g, const double* _
     if (threadIdx.x == 0) { red_a[red_off + blockIdx.x] = sa; red_b[red_off + blockIdx.x] = sb; }
 }
 
-template <int S>
+template <int NV, int NC>
 __global__ __launch_bounds__(kBlock) void k_init_z(GroupDev g, const double* __restrict__ xfull, double* __restrict__ z) {
-    constexpr int D = 3 * shape_nc(S);
+    constexpr int D = 3 * NC;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= g.count) return;
     double F[D];
-    gather_P<S>(g, e, xfull, F);
+    gather_P<NV, NC>(g, e, xfull, F);
 #pragma unroll
     for (int i = 0; i < D; ++i) z[g.zoff + (size_t)i * g.count + e] = F[i];
 }
@@ -1857,6 +1854,31 @@ __global__ __launch_bounds__(kSolveBlock) void k_test_cod(int n, const double* _
     if ((int)threadIdx.x < n) x[threadIdx.x] = sx[threadIdx.x];
 }
 
+// The one place a group's kind (and a tie's vertex count) becomes a kernel's shape: f is called with
+// std::integral_constant<int, shape(kind, nv)>. What is not shape -- HYPER from g.mat, the material
+// or mesh-table pack -- the launchers decide inside f.
+template <ElemKind K, int NV>
+using ShapeC = std::integral_constant<int, shape(K, NV)>;
+template <class F>
+void with_shape(const GroupDev& g, F&& f) {
+    switch (g.kind) {
+    case kTet: return f(ShapeC<kTet, 4>{});
+    case kTri: return f(ShapeC<kTri, 3>{});
+    case kCollision: return f(ShapeC<kCollision, 1>{});
+    case kHinge: return f(ShapeC<kHinge, 4>{});
+    case kSpring: return f(ShapeC<kSpring, 2>{});
+    case kTie:   // one instantiation per vertex count
+        switch (g.nv) {
+        case 3: return f(ShapeC<kTie, 3>{});
+        case 4: return f(ShapeC<kTie, 4>{});
+        case 5: return f(ShapeC<kTie, 5>{});
+        case 6: return f(ShapeC<kTie, 6>{});
+        }
+        throw Error(ERR_STATE, "element kernels: a tie group with " + std::to_string(g.nv) + " vertices (3 to 6 are provided)");
+    }
+    throw Error(ERR_STATE, "element kernels: unknown group kind " + std::to_string((int)g.kind));
+}
+
 }  // namespace
 
 // ============================================================================ launchers
@@ -1888,7 +1910,7 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
                     const GroupVar& var, const MeshObsDev* meshes) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 0 && g.mat != 0 && !red && queue && queue->counter) {   // hyperelastic, no partials: work queue
+    if (g.kind == kTet && g.mat != 0 && !red && queue && queue->counter) {   // hyperelastic, no partials: work queue
         // k_local_z_hq / k_local_z_hqf reset the queue themselves (queue_reset_last); k_local_z_hq2 does not.
         // A per-element group never takes k_local_z_hq2: AA_LQ_SPLIT is ignored for it.
         const bool split = queue->split && !var;
@@ -1922,26 +1944,29 @@ void launch_local_z(const GroupDev& g, const double* xfull, const double* u, dou
         AA_CHECK_LAUNCH();
         return;
     }
-    if (g.kind == 5) {   // ties: one instantiation per vertex count
-        if (g.nv == 3) hipLaunchKernelGGL((k_local_z<shape_tie(3), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
-        else if (g.nv == 4) hipLaunchKernelGGL((k_local_z<shape_tie(4), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
-        else if (g.nv == 5) hipLaunchKernelGGL((k_local_z<shape_tie(5), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
-        else hipLaunchKernelGGL((k_local_z<shape_tie(6), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
-    }
-    else if (g.kind == 4) hipLaunchKernelGGL((k_local_z<kShapeSpring, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
-    else if (g.kind == 3) hipLaunchKernelGGL((k_local_z<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
-    else if (g.kind == 2 && meshes) hipLaunchKernelGGL((k_local_z<1, 0, const MeshObsDev*>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, meshes);
-    else if (g.kind == 2) hipLaunchKernelGGL((k_local_z<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
-    else if (g.kind == 1 && var) hipLaunchKernelGGL((k_local_z<3, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, var);
-    else if (g.kind == 1) hipLaunchKernelGGL((k_local_z<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
-    else if (g.mat == 0) hipLaunchKernelGGL((k_local_z<4, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);   // the linear prox reads w only
-    else if (var) hipLaunchKernelGGL((k_local_z<4, 1, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, var);
-    else hipLaunchKernelGGL((k_local_z<4, 1>), dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off);
+    with_shape(g, [&](auto shape_c) {
+        constexpr int S = decltype(shape_c)::value;
+        constexpr ElemKind K = shape_kind(S);
+        auto go = [&](auto kernel, auto... pack) {
+            hipLaunchKernelGGL(kernel, dim3(nb), dim3(kBlock), 0, s, g, xfull, u, z, y, nf, variant, mode, ctrl, red, red_off, pack...);
+        };
+        if constexpr (K == kTet) {
+            if (g.mat == 0) go(k_local_z<S, 0>);   // the linear prox reads w only
+            else if (var) go(k_local_z<S, 1, GroupVar>, var);
+            else go(k_local_z<S, 1>);
+        } else if constexpr (K == kTri) {
+            if (var) go(k_local_z<S, 0, GroupVar>, var);
+            else go(k_local_z<S, 0>);
+        } else if constexpr (K == kCollision) {
+            if (meshes) go(k_local_z<S, 0, const MeshObsDev*>, meshes);
+            else go(k_local_z<S, 0>);
+        } else go(k_local_z<S, 0>);
+    });
     AA_CHECK_LAUNCH();
 }
 
 bool local_z_res_ok(const GroupDev& g, const LocalQueue* queue) {
-    return g.kind == 0 && g.mat != 0 && !g.pinned && queue && queue->counter && queue->fused && !queue->split;
+    return g.kind == kTet && g.mat != 0 && !g.pinned && queue && queue->counter && queue->fused && !queue->split;
 }
 
 void launch_local_z_res(const GroupDev& g, const double* xfull, const double* u, const double* zref, double* pe, int nf,
@@ -1968,17 +1993,10 @@ void launch_resid_update_u(const GroupDev& g, const double* xfull, const double*
                            int nf, Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 5) {   // ties: one instantiation per vertex count
-        if (g.nv == 3) hipLaunchKernelGGL(k_resid_u<shape_tie(3)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
-        else if (g.nv == 4) hipLaunchKernelGGL(k_resid_u<shape_tie(4)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
-        else if (g.nv == 5) hipLaunchKernelGGL(k_resid_u<shape_tie(5)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
-        else hipLaunchKernelGGL(k_resid_u<shape_tie(6)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
-    }
-    else if (g.kind == 4) hipLaunchKernelGGL(k_resid_u<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
-    else if (g.kind == 3) hipLaunchKernelGGL(k_resid_u<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
-    else if (g.kind == 2) hipLaunchKernelGGL(k_resid_u<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
-    else if (g.kind == 1) hipLaunchKernelGGL(k_resid_u<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
-    else hipLaunchKernelGGL(k_resid_u<4>, dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+    with_shape(g, [&](auto shape_c) {
+        constexpr int S = decltype(shape_c)::value;
+        hipLaunchKernelGGL((k_resid_u<shape_nv(S), shape_nc(S)>), dim3(nb), dim3(kBlock), 0, s, g, xfull, xlast, z, u, nf, ctrl, red_a, red_b, red_off);
+    });
     AA_CHECK_LAUNCH();
 }
 
@@ -1986,20 +2004,18 @@ void launch_u_and_y(const GroupDev& g, const double* xfull, const double* z, con
                     int nf, int mode, int redo, Ctrl* ctrl, hipStream_t s, const GroupVar& var) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 5) {   // ties: one instantiation per vertex count
-        if (g.nv == 3) hipLaunchKernelGGL((k_u_and_y<shape_tie(3), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
-        else if (g.nv == 4) hipLaunchKernelGGL((k_u_and_y<shape_tie(4), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
-        else if (g.nv == 5) hipLaunchKernelGGL((k_u_and_y<shape_tie(5), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
-        else hipLaunchKernelGGL((k_u_and_y<shape_tie(6), 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
-    }
-    else if (g.kind == 4) hipLaunchKernelGGL((k_u_and_y<kShapeSpring, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
-    else if (g.kind == 3) hipLaunchKernelGGL((k_u_and_y<kShapeHinge, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
-    else if (g.kind == 2) hipLaunchKernelGGL((k_u_and_y<1, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
-    else if (g.kind == 1) hipLaunchKernelGGL((k_u_and_y<3, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);   // no material reads
-    else if (g.mat == 0 && var) hipLaunchKernelGGL((k_u_and_y<4, 0, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl, var);
-    else if (g.mat == 0) hipLaunchKernelGGL((k_u_and_y<4, 0>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
-    else if (var) hipLaunchKernelGGL((k_u_and_y<4, 1, GroupVar>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl, var);
-    else hipLaunchKernelGGL((k_u_and_y<4, 1>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl);
+    with_shape(g, [&](auto shape_c) {
+        constexpr int S = decltype(shape_c)::value;
+        auto go = [&](auto kernel, auto... pack) {
+            hipLaunchKernelGGL(kernel, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, uin, u, y, nf, mode, redo, ctrl, pack...);
+        };
+        if constexpr (shape_kind(S) == kTet) {
+            if (g.mat == 0 && var) go(k_u_and_y<S, 0, GroupVar>, var);
+            else if (g.mat == 0) go(k_u_and_y<S, 0>);
+            else if (var) go(k_u_and_y<S, 1, GroupVar>, var);
+            else go(k_u_and_y<S, 1>);
+        } else go(k_u_and_y<S, 0>);   // no material reads
+    });
     AA_CHECK_LAUNCH();
 }
 
@@ -2007,34 +2023,20 @@ void launch_prim_z(const GroupDev& g, const double* xfull, const double* z, cons
                    Ctrl* ctrl, double* red_a, double* red_b, int red_off, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 5) {   // ties: one instantiation per vertex count
-        if (g.nv == 3) hipLaunchKernelGGL(k_prim_z<shape_tie(3)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
-        else if (g.nv == 4) hipLaunchKernelGGL(k_prim_z<shape_tie(4)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
-        else if (g.nv == 5) hipLaunchKernelGGL(k_prim_z<shape_tie(5)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
-        else hipLaunchKernelGGL(k_prim_z<shape_tie(6)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
-    }
-    else if (g.kind == 4) hipLaunchKernelGGL(k_prim_z<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
-    else if (g.kind == 3) hipLaunchKernelGGL(k_prim_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
-    else if (g.kind == 2) hipLaunchKernelGGL(k_prim_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
-    else if (g.kind == 1) hipLaunchKernelGGL(k_prim_z<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
-    else hipLaunchKernelGGL(k_prim_z<4>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+    with_shape(g, [&](auto shape_c) {
+        constexpr int S = decltype(shape_c)::value;
+        hipLaunchKernelGGL((k_prim_z<shape_nv(S), shape_nc(S)>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z, zref, nf, redo, ctrl, red_a, red_b, red_off);
+    });
     AA_CHECK_LAUNCH();
 }
 
 void launch_init_z(const GroupDev& g, const double* xfull, double* z, hipStream_t s) {
     if (g.count == 0) return;
     const int nb = blocks_for(g.count);
-    if (g.kind == 5) {   // ties: one instantiation per vertex count
-        if (g.nv == 3) hipLaunchKernelGGL(k_init_z<shape_tie(3)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
-        else if (g.nv == 4) hipLaunchKernelGGL(k_init_z<shape_tie(4)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
-        else if (g.nv == 5) hipLaunchKernelGGL(k_init_z<shape_tie(5)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
-        else hipLaunchKernelGGL(k_init_z<shape_tie(6)>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
-    }
-    else if (g.kind == 4) hipLaunchKernelGGL(k_init_z<kShapeSpring>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
-    else if (g.kind == 3) hipLaunchKernelGGL(k_init_z<kShapeHinge>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
-    else if (g.kind == 2) hipLaunchKernelGGL(k_init_z<1>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
-    else if (g.kind == 1) hipLaunchKernelGGL(k_init_z<3>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
-    else hipLaunchKernelGGL(k_init_z<4>, dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+    with_shape(g, [&](auto shape_c) {
+        constexpr int S = decltype(shape_c)::value;
+        hipLaunchKernelGGL((k_init_z<shape_nv(S), shape_nc(S)>), dim3(nb), dim3(kBlock), 0, s, g, xfull, z);
+    });
     AA_CHECK_LAUNCH();
 }
 

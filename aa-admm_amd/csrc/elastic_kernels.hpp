@@ -9,10 +9,15 @@ namespace aa {
 constexpr int kMaxM = 32;          // largest Anderson window supported on device
 constexpr double kCombEps = 1e-20; // Solver.cpp:93 eps
 
+// The kinds of energy term (kCollision: CollisionEnergyTerm.hpp:41-117). The values are fixed: the
+// C ABI's add_tets / add_tris mean 0 and 1. What each kind is stands in kind_traits below.
+enum ElemKind : int { kTet = 0, kTri = 1, kCollision = 2, kHinge = 3, kSpring = 4, kTie = 5 };
+constexpr int kNumKinds = 6;
+
 // One homogeneous block of energy terms (same kind / material / Lame), SoA on device.
 struct GroupDev {
-    int kind;            // 0 tet, 1 tri, 2 collision point (CollisionEnergyTerm.hpp:41-117), 3 bending hinge, 4 spring, 5 tie
-    int mat;             // 0 linear, 1 NeoHookean, 2 StVK; kinds 4, 5: the spring mode (AA_SPRING_*)
+    ElemKind kind;       // an int in size and place: every element kernel takes GroupDev first, by value
+    int mat;             // 0 linear, 1 NeoHookean, 2 StVK; KindTraits::mode_in_mat: the spring mode
     int count;           // elements
     int nv, ncol, dim;   // 4/3/9 for tets, 3/2/6 for tris
     int pinned;          // some element of the group has a pinned node (C_fix terms exist)
@@ -22,7 +27,7 @@ struct GroupDev {
     const int* spos;     // [nv][count] position of the vertex's rhs slot (node order), -1 = pinned
     const double* G;     // [(c*nv + a)][count]  F[:,c] = sum_a G[c][a] x_a
     const double* w;     // [count] ADMM weights sqrt(k*vol)
-    const double* vol;   // [count]
+    const double* vol;   // [count]; KindTraits::rest_in_vol: the rest length
     double mu, lambda, k, lmin, lmax;
     const double* obs;   // collision points: the obstacle table (obs[0] = count, then kObsStride per obstacle)
 };
@@ -59,24 +64,59 @@ struct MeshCarryDev {
     const double* vprev;     // [nv][3] the vertices in force during the previous step's pass
     const int* leaf_vid;     // [tris][3] vertex ids of leaf triangle k (MeshRefitTables::leaf_vid)
 };
-__host__ __device__ constexpr int ncol_of(int nv) { return nv > 1 ? nv - 1 : 1; }   // 1 vertex: identity reduction
-// The element kernels' shape parameter S: a vertex count (1, 3, 4: the simplex shapes, ncol_of(S)
-// columns), or 16 nv + ncol for a shape whose column count is its own. kShapeHinge: the bending
-// hinge (GroupDev::kind 3), four vertices and the one column z = K x; its rest length r[count]
-// rides in GroupDev::vol, which no kernel reads for this kind otherwise.
-constexpr int kShapeHinge = 16 * 4 + 1;
-// kShapeSpring: the two-node spring (GroupDev::kind 4), row (-1, +1), the one column z = x_b - x_a;
-// its rest length L[count] rides in GroupDev::vol like the hinge's r, its mode in GroupDev::mat.
-constexpr int kShapeSpring = 16 * 2 + 1;
-// shape_tie(nv): a tie (GroupDev::kind 5, ties.hpp), nv = na + nb = 3..6 vertices and the one column
-// z = sum_j b_j x_Bj - sum_i a_i x_Ai (row (-a, +b) in G); L in GroupDev::vol and the mode in
-// GroupDev::mat as for a spring. 16 * 4 + 1 is the hinge already, so a tie carries a tag above bit 8,
-// which shape_nv / shape_nc mask off.
-constexpr int kShapeTieTag = 256;
-__host__ __device__ constexpr int shape_tie(int nv) { return kShapeTieTag + 16 * nv + 1; }
-__host__ __device__ constexpr bool shape_is_tie(int s) { return s >= kShapeTieTag; }
-__host__ __device__ constexpr int shape_nv(int s) { return s < 16 ? s : (s & 255) / 16; }
-__host__ __device__ constexpr int shape_nc(int s) { return s < 16 ? ncol_of(s) : s % 16; }
+__host__ __device__ constexpr int ncol_of(int nv) { return nv - 1; }   // a simplex: its edge columns
+
+// What a kind is, in one place. Host messages, the byte model, initialize's refusals, the shape
+// below and the kernels' branches all read this table; a new kind is a row here (DESIGN.md §3.3,
+// "Element kinds").
+struct KindTraits {
+    const char* noun;      // "the solver has <noun>", "<noun> exist in the (u,x) variant only"
+    const char* term;      // one element, and "no <term> term"
+    const char* needs;     // "(<needs> one rank)"
+    int nv_min, nv_max;    // admissible vertex counts
+    bool one_col;          // one column z (3 doubles) per element; false: the simplex's nv - 1 columns
+    bool rest_in_vol;      // GroupDev::vol holds a rest length (the hinge's r, a spring's or tie's L)
+    bool mode_in_mat;      // GroupDev::mat holds the spring mode (AA_SPRING_*), not a material
+    bool z_and_ranks;      // the z variant and partitioned solvers take it; false: initialize refuses both
+};
+__host__ __device__ constexpr KindTraits kind_traits(ElemKind k) {
+    switch (k) {
+    case kTet:       return {"tets", "tet", "tets need", 4, 4, false, false, false, true};
+    case kTri:       return {"triangles", "triangle", "triangles need", 3, 3, false, false, false, true};
+    // (the z variant refuses collision points in the reference's own words, before this table is asked)
+    case kCollision: return {"collision points", "collision", "collisions need", 1, 1, true, false, false, true};
+    // G holds K (bending.hpp), the one column is z = K x
+    case kHinge:     return {"bending hinges", "hinge", "bending needs", 4, 4, true, true, false, false};
+    // G = (-1, +1), z = x_b - x_a (springs.hpp)
+    case kSpring:    return {"springs", "spring", "springs need", 2, 2, true, true, true, false};
+    // nv = na + nb, G = (-a, +b), z = sum_j b_j x_Bj - sum_i a_i x_Ai (ties.hpp); else as a spring
+    case kTie:       return {"ties", "tie", "ties need", 3, 6, true, true, true, false};
+    }
+    return {"", "", "", 0, 0, false, false, false, false};
+}
+__host__ __device__ constexpr int kind_ncol(ElemKind k, int nv) { return kind_traits(k).one_col ? 1 : nv - 1; }
+
+// The element kernels' shape parameter S says the kind and the vertex count: 100 kind + nv, so a
+// kernel's name in a profile reads e.g. <503, 0> = a three-vertex tie.
+__host__ __device__ constexpr int shape(ElemKind k, int nv) { return 100 * (int)k + nv; }
+__host__ __device__ constexpr ElemKind shape_kind(int s) { return (ElemKind)(s / 100); }
+__host__ __device__ constexpr int shape_nv(int s) { return s % 100; }
+__host__ __device__ constexpr int shape_nc(int s) { return kind_ncol(shape_kind(s), shape_nv(s)); }
+// every kind and admissible nv: the shape gives back what made it, and no two pairs share one
+constexpr bool shapes_ok() {
+    for (int k = 0; k < kNumKinds; ++k) {
+        const KindTraits t = kind_traits((ElemKind)k);
+        for (int nv = t.nv_min; nv <= t.nv_max; ++nv) {
+            const int s = shape((ElemKind)k, nv);
+            if (shape_kind(s) != k || shape_nv(s) != nv || shape_nc(s) != (t.one_col ? 1 : nv - 1)) return false;
+            for (int k2 = 0; k2 < k; ++k2)
+                for (int nv2 = kind_traits((ElemKind)k2).nv_min; nv2 <= kind_traits((ElemKind)k2).nv_max; ++nv2)
+                    if (shape((ElemKind)k2, nv2) == s) return false;
+        }
+    }
+    return true;
+}
+static_assert(shapes_ok(), "shape(kind, nv) must round-trip, give the traits' column count and be unique");
 
 // Device-side control block: residual bookkeeping, reject/done flags, Anderson state.
 struct Ctrl {

@@ -42,10 +42,11 @@ def function_name(mangled):   # ..._GLOBAL__N_1<len><name>I... -> <name>
 
 def main(old_path, new_path):
     old, new = kernels(old_path), kernels(new_path)
-    same, renamed, bad = 0, [], []
+    same, renamed, bad, hits = 0, [], [], set()
     for name, (body, desc) in sorted(old.items()):
         cands = [name] if name in new else [k for k in new if k not in old and function_name(k) == function_name(name)]
-        hit = next((k for k in cands if text(new[k][0], k) == text(body, name)), None)
+        match = [k for k in cands if text(new[k][0], k) == text(body, name)]
+        hit = next((k for k in match if k not in hits), match[0] if match else None)   # an unclaimed one first
         if hit is None:
             bad.append(f"{name}: no kernel with this text ({len(cands)} candidates)")
             continue
@@ -54,10 +55,12 @@ def main(old_path, new_path):
             bad.append(f"{name}: descriptor differs {diff}")
             continue
         same += 1
+        hits.add(hit)
         if hit != name:
             renamed.append((name, hit))
     print(f"{len(old)} kernels in {old_path}, {len(new)} in {new_path}: {same} unchanged "
-          f"({len(renamed)} under a new name), {len(bad)} changed, {len(new) - same} new")
+          f"({len(renamed)} under a new name, {same - len(hits)} sharing a kernel with another), {len(bad)} changed, "
+          f"{len(set(new) - hits)} new")
     for a, b in renamed:
         print("  renamed", a, "->", b)
     for b in bad:
