@@ -43,6 +43,7 @@ EXPORTS = [
     "aa_test_prox", "aa_test_cod_solve", "aa_test_geom_project", "aa_test_mesh_sdf", "aa_test_collision_prox",
     "aa_test_mesh_sdf_posed", "aa_test_collision_prox_posed", "aa_test_mesh_refit_tables", "aa_test_mesh_sdf_deformed", "aa_test_direct_solve",
     "aa_test_bound_refit", "aa_test_collision_prox_exempt", "aa_test_contact_friction", "aa_test_contact_friction_carry",
+    "aa_test_anderson_step",
 ]
 
 # Geometry constraint types (Geometry/Constraint.h) and SPD solver types (SolverCommon.h)
@@ -1351,3 +1352,51 @@ def test_direct_solve(ctx: Context, A, xyz, b0, b1=None, script=(AA_SOLVE_B0,), 
         raise RuntimeError(f"PlanSummary has {cnt.value} fields, the binding names {len(SOLVE_PLAN_FIELDS)}")
     return DirectSolveResult([(x[k, 0], x[k, 1]) for k in range(len(sc))], (xh[0], xh[1] if b1 is not None else None),
                              dict(zip(SOLVE_PLAN_FIELDS, (int(v) for v in plan))), info[:, 0].copy(), info[:, 1].copy())
+
+
+# flags of aa_test_anderson_step (include/aa_admm.h)
+AA_STEP_COPY_TO, AA_STEP_INPLACE, AA_STEP_NARROW, AA_STEP_ROWS = 1, 2, 4, 8
+ANDERSON_CTL = ("aa_iter", "aa_col", "aa_skip", "aa_active", "done", "aa_mk", "aa_j", "aa_jn", "aa_first")
+
+
+def hook_anderson_step(ctx: Context, state, G, nblocks=0, copy_to=None, out=None, inplace=False, narrow=True, rows=False):
+    """aa_test_anderson_step: one launch_aa_reduce -> launch_aa_solve -> launch_aa_mix on the state.
+
+    state: dict with m, na, nb, eff, cur (dim), dF (m, eff), dG (m, dim) -- row c = history column
+    c --, the ANDERSON_CTL ints, scale (m), M (m, m) with M[r, c] the device's M[c * m + r], coef (m),
+    aa_s and mask = (lo1, hi1, lo2, hi2). out / copy_to: what the buffers hold on entry (None with
+    inplace / without the copy). Returns a dict: the same keys after the step, plus red (blocks,
+    2 + 2 bucket), out, copy_to (None where not used), bucket, nblocks and cols (1 / 0 / -1)."""
+    m, na, nb, eff = int(state["m"]), int(state["na"]), int(state["nb"]), int(state["eff"])
+    dim = na + nb
+    G = np.ascontiguousarray(G, np.float64).reshape(-1)
+    cur = np.array(state["cur"], np.float64).reshape(-1)
+    dF = np.array(state["dF"], np.float64, order="C")
+    dG = np.array(state["dG"], np.float64, order="C")
+    ok = m >= 1 and len(G) == dim and len(cur) == dim and 0 < eff <= dim and dF.shape == (m, eff) and dG.shape == (m, dim)
+    if not ok:
+        raise ValueError("hook_anderson_step: array shapes do not fit m, na, nb, eff")
+    ctl = np.array([state[k] for k in ANDERSON_CTL], np.int32)
+    scale = np.array(state["scale"], np.float64).reshape(m)
+    M = np.array(np.asarray(state["M"], np.float64).reshape(m, m).T, order="C")   # device: column-major
+    coef = np.array(state["coef"], np.float64).reshape(m)
+    aa_s = C.c_double(float(state["aa_s"]))
+    mask = np.array(state["mask"], np.int64).reshape(4)
+    flags = ((AA_STEP_COPY_TO if copy_to is not None else 0) | (AA_STEP_INPLACE if inplace else 0)
+             | (AA_STEP_NARROW if narrow else 0) | (AA_STEP_ROWS if rows else 0))
+    o = None if inplace else np.array(out, np.float64).reshape(dim)
+    cp = None if copy_to is None else np.array(copy_to, np.float64).reshape(dim)
+    cap = (nblocks if nblocks > 0 else max(1, (dim + 63) // 64)) * 66   # blocks hold at least a wave's rows
+    red = np.zeros(cap)
+    info = np.zeros(3, np.int32)
+    _chk(lib().aa_test_anderson_step(
+        ctx.h, C.c_int(m), C.c_longlong(na), C.c_longlong(nb), C.c_longlong(eff), _dp(G), _dp(cur), _dp(dF), _dp(dG),
+        _ip(ctl), _dp(scale), _dp(M), _dp(coef), C.byref(aa_s), mask.ctypes.data_as(C.POINTER(C.c_longlong)),
+        C.c_int(nblocks), C.c_int(flags), _dp(red), C.c_longlong(cap), None if o is None else _dp(o),
+        None if cp is None else _dp(cp), _ip(info)))
+    bucket, nbl = int(info[0]), int(info[1])
+    res = dict(m=m, na=na, nb=nb, eff=eff, cur=cur, dF=dF, dG=dG, scale=scale, M=np.array(M.T, order="C"), coef=coef,
+               aa_s=aa_s.value, mask=tuple(int(v) for v in mask), red=red[:nbl * (2 + 2 * bucket)].reshape(nbl, 2 + 2 * bucket).copy(),
+               out=o, copy_to=cp, bucket=bucket, nblocks=nbl, cols=int(info[2]))
+    res.update({k: int(v) for k, v in zip(ANDERSON_CTL, ctl)})
+    return res

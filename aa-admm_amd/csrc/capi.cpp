@@ -1336,3 +1336,79 @@ extern "C" int aa_test_geom_project(aa_ctx ctx, int type, int k, const double* p
     });
 }
 
+
+extern "C" int aa_test_anderson_step(aa_ctx ctx, int m, long long na, long long nb, long long eff, const double* G,
+                                     double* cur, double* dF, double* dG, int* ctl9, double* scale, double* M,
+                                     double* coef, double* aa_s, const long long* mask4, int nblocks, int flags,
+                                     double* red, long long red_cap, double* out, double* copy_to, int* info3) {
+    return with_device_arrays(ctx, [&](hipStream_t s) {
+        const long long dim = na + nb;
+        NEED(G && cur && dF && dG && ctl9 && scale && M && coef && aa_s && mask4 && red && info3,
+             "aa_test_anderson_step: null argument");
+        NEED(m >= 1 && m <= aa::kMaxM, "aa_test_anderson_step: m must lie in 1..32");
+        NEED(na >= 0 && nb >= 0 && dim >= 1 && dim < (1LL << 31), "aa_test_anderson_step: bad segment lengths");
+        NEED(eff > 0 && eff <= dim, "aa_test_anderson_step: eff must lie in 1..dim");
+        NEED(ctl9[0] >= 0, "aa_test_anderson_step: aa_iter must not be negative");
+        NEED(ctl9[1] >= 0 && ctl9[1] < m, "aa_test_anderson_step: aa_col must lie in 0..m-1");
+        NEED(nblocks >= 0 && nblocks <= 2048, "aa_test_anderson_step: nblocks must lie in 0..2048");
+        const bool want_copy = flags & AA_STEP_COPY_TO, inplace = flags & AA_STEP_INPLACE;
+        NEED(!(flags & ~(AA_STEP_COPY_TO | AA_STEP_INPLACE | AA_STEP_NARROW | AA_STEP_ROWS)), "aa_test_anderson_step: unknown flag");
+        NEED(!inplace || nb == 0, "aa_test_anderson_step: the in-place form has one segment");
+        NEED(inplace || out, "aa_test_anderson_step: out is null");
+        NEED(!want_copy || copy_to, "aa_test_anderson_step: copy_to is null");
+        const int nbl = nblocks > 0 ? nblocks : aa::aa_reduce_blocks(dim);
+        const int bucket = aa::aa_window_bucket(m);
+        const size_t nred = (size_t)nbl * (2 + 2 * bucket);
+        NEED(red_cap >= (long long)nred, "aa_test_anderson_step: red is too short");
+
+        aa::Ctrl hc{};
+        hc.aa_m = m;
+        hc.aa_iter = ctl9[0]; hc.aa_col = ctl9[1]; hc.aa_skip = ctl9[2]; hc.aa_active = ctl9[3]; hc.done = ctl9[4];
+        hc.aa_mk = ctl9[5]; hc.aa_j = ctl9[6]; hc.aa_jn = ctl9[7]; hc.aa_first = ctl9[8];
+        hc.aa_s = *aa_s;
+        std::copy(scale, scale + m, hc.scale);
+        std::copy(coef, coef + m, hc.coef);
+        std::copy(M, M + (size_t)m * m, hc.M);
+        aa::DevBuf<aa::Ctrl> dctrl(1);
+        // the two segments live apart, as the solvers' do
+        aa::DevBuf<double> dGa, dGb, dcur, ddF, ddG, dred(nred), douta, doutb, dcpa, dcpb;
+        dGa.upload(G, (size_t)na, s);
+        dGb.upload(G + na, (size_t)nb, s);
+        dcur.upload(cur, (size_t)dim, s);
+        ddF.upload(dF, (size_t)m * eff, s);
+        ddG.upload(dG, (size_t)m * dim, s);
+        dred.zero(s);
+        if (!inplace) { douta.upload(out, (size_t)na, s); doutb.upload(out + na, (size_t)nb, s); }
+        if (want_copy) { dcpa.upload(copy_to, (size_t)na, s); dcpb.upload(copy_to + na, (size_t)nb, s); }
+        AA_HIP(hipMemcpyAsync(dctrl.p, &hc, sizeof(hc), hipMemcpyHostToDevice, s));
+        AA_HIP(hipStreamSynchronize(s));   // (hc is pageable host memory)
+
+        // a segment of no entries is still a pointer the kernels may form addresses from
+        const aa::Seg2 g{na ? dGa.p : dGb.p, na, dGb.p, nb};
+        const aa::Seg2 o = inplace ? aa::Seg2{dcur.p, dim, nullptr, 0} : aa::Seg2{na ? douta.p : doutb.p, na, doutb.p, nb};
+        const aa::Seg2 cp = want_copy ? aa::Seg2{na ? dcpa.p : dcpb.p, na, dcpb.p, nb} : aa::Seg2{nullptr, 0, nullptr, 0};
+        aa::AAMask mask;
+        mask.lo1 = mask4[0]; mask.hi1 = mask4[1]; mask.lo2 = mask4[2]; mask.hi2 = mask4[3];
+        const int cols = (flags & AA_STEP_ROWS) ? 0 : 1;
+        aa::launch_aa_reduce(g, dcur.p, eff, ddF.p, ddG.p, dctrl.p, dred.p, nbl, cp, m, s, nullptr, nullptr, 0, nullptr,
+                             nullptr, nullptr, mask, cols);
+        aa::launch_aa_solve(dctrl.p, dred.p, nbl, m, s);
+        aa::launch_aa_mix(g, dcur.p, eff, ddF.p, ddG.p, dctrl.p, o, m, s, (flags & AA_STEP_NARROW) != 0);
+
+        auto down = [&](double* h, const aa::DevBuf<double>& d) {
+            if (d.n) AA_HIP(hipMemcpyAsync(h, d.p, d.bytes(), hipMemcpyDeviceToHost, s));
+        };
+        down(red, dred); down(cur, dcur); down(dF, ddF); down(dG, ddG);
+        if (!inplace) { down(out, douta); down(out + na, doutb); }
+        if (want_copy) { down(copy_to, dcpa); down(copy_to + na, dcpb); }
+        AA_HIP(hipMemcpyAsync(&hc, dctrl.p, sizeof(hc), hipMemcpyDeviceToHost, s));
+        AA_HIP(hipStreamSynchronize(s));
+        ctl9[0] = hc.aa_iter; ctl9[1] = hc.aa_col; ctl9[2] = hc.aa_skip; ctl9[3] = hc.aa_active; ctl9[4] = hc.done;
+        ctl9[5] = hc.aa_mk; ctl9[6] = hc.aa_j; ctl9[7] = hc.aa_jn; ctl9[8] = hc.aa_first;
+        *aa_s = hc.aa_s;
+        std::copy(hc.scale, hc.scale + m, scale);
+        std::copy(hc.coef, hc.coef + m, coef);
+        std::copy(hc.M, hc.M + (size_t)m * m, M);
+        info3[0] = bucket; info3[1] = nbl; info3[2] = bucket == 32 ? cols : -1;
+    });
+}

@@ -2218,14 +2218,14 @@ static bool aa_cols() {
 
 void launch_aa_reduce(Seg2 G, const double* cur, long long eff, double* dF, double* dG, Ctrl* ctrl, double* red,
                       int nblocks, Seg2 copy_to, int m, hipStream_t s, const double* comb_a, const double* comb_b,
-                      int comb_nb, double* hist_prim, double* hist_comb, int* hist_rej, AAMask mask) {
+                      int comb_nb, double* hist_prim, double* hist_comb, int* hist_rej, AAMask mask, int cols) {
 #define AA_RED_ARGS G, cur, eff, dF, dG, ctrl, red, copy_to, comb_a, comb_b, comb_nb, hist_prim, hist_comb, hist_rej, mask
     switch (mm_bucket(m)) {
         case 8: hipLaunchKernelGGL(k_aa_reduce<8>, dim3(nblocks), dim3(kBlock), 0, s, AA_RED_ARGS); break;
         case 12: hipLaunchKernelGGL(k_aa_reduce<12>, dim3(nblocks), dim3(kBlock), 0, s, AA_RED_ARGS); break;
         case 16: hipLaunchKernelGGL(k_aa_reduce<16>, dim3(nblocks), dim3(kBlock), 0, s, AA_RED_ARGS); break;
         default:   // m > 16: column-parallel (AA_AA_COLS=0: the row-parallel kernel)
-            if (aa_cols()) hipLaunchKernelGGL(k_aa_reduce_cols<32>, dim3(nblocks), dim3(kBlock), 0, s, AA_RED_ARGS);
+            if (cols < 0 ? aa_cols() : cols != 0) hipLaunchKernelGGL(k_aa_reduce_cols<32>, dim3(nblocks), dim3(kBlock), 0, s, AA_RED_ARGS);
             else hipLaunchKernelGGL(k_aa_reduce<32>, dim3(nblocks), dim3(kBlock), 0, s, AA_RED_ARGS);
             break;
     }

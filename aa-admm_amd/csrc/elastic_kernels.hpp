@@ -260,10 +260,12 @@ void launch_wind(const int* tris3, const int* tri_ord, const int* lvl_ptr, int n
 int aa_window_bucket(int m);
 int aa_reduce_blocks(long long dim);
 // comb_a/comb_b given: the UX combined residual, break test and record are fused in front
+// cols: the 32 bucket's kernel, 1 column-parallel, 0 row-parallel, -1 (every solver) as AA_AA_COLS
+// says; aa_test_anderson_step alone names one
 void launch_aa_reduce(Seg2 G, const double* cur, long long eff, double* dF, double* dG, Ctrl* ctrl, double* red,
                       int nblocks, Seg2 copy_to, int m, hipStream_t s, const double* comb_a = nullptr,
                       const double* comb_b = nullptr, int comb_nb = 0, double* hist_prim = nullptr,
-                      double* hist_comb = nullptr, int* hist_rej = nullptr, AAMask mask = AAMask());
+                      double* hist_comb = nullptr, int* hist_rej = nullptr, AAMask mask = AAMask(), int cols = -1);
 void launch_aa_solve(Ctrl* ctrl, const double* red, int nblocks, int m, hipStream_t s);
 void launch_aa_mix(Seg2 G, double* cur, long long eff, double* dF, double* dG, Ctrl* ctrl, Seg2 out, int m,
                    hipStream_t s, bool narrow = true);

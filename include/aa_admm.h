@@ -743,6 +743,28 @@ int aa_test_direct_solve(aa_ctx ctx, int n, const double* xyz3, const int* ptr, 
                          int device_factor, const double* b0, const double* b1, int n_script, const int* script,
                          double sentinel, double* x_out, double* x_host, int* row_info, int* plan, int plan_cap,
                          int* plan_count);
+/* One Anderson step (AndersonAcceleration::compute_impl, AndersonAcceleration.h:154-211) from a
+ * caller-given state: the solvers' own launch_aa_reduce -> launch_aa_solve -> launch_aa_mix on
+ * uploaded arrays, without the fused combined-residual head, and everything they can write handed
+ * back. The two segments of G (na then nb entries; dim = na + nb), of out and of copy_to are
+ * separate device allocations.
+ *   in/out: cur (dim), dF (m x eff, column stride eff), dG (m x dim), ctl9 = {aa_iter, aa_col,
+ *     aa_skip, aa_active, done, aa_mk, aa_j, aa_jn, aa_first}, scale (m), M (m x m column-major),
+ *     coef (m), aa_s, out (dim; what it holds on entry is uploaded, so an untouched out shows;
+ *     ignored with AA_STEP_INPLACE), copy_to (dim, likewise; read with AA_STEP_COPY_TO only)
+ *   mask4 = {lo1, hi1, lo2, hi2}: the AAMask windows in the second segment
+ *   nblocks: blocks of the reduce, 0 = what the solvers take for this dim
+ *   flags: AA_STEP_COPY_TO the reduce copies G; AA_STEP_INPLACE out.a == cur (nb must be 0);
+ *     AA_STEP_NARROW launch_aa_mix's narrow instantiations for m <= 7; AA_STEP_ROWS the
+ *     row-parallel reduce for m > 16 (default there: the column-parallel one)
+ *   red: the reduce's block partials, info3[1] x (2 + 2 info3[0]) doubles (red_cap = its capacity;
+ *     zero where the kernels wrote nothing); info3 = {aa_window_bucket(m), blocks, 1 cols / 0 rows /
+ *     -1 not the 32 bucket} */
+enum { AA_STEP_COPY_TO = 1, AA_STEP_INPLACE = 2, AA_STEP_NARROW = 4, AA_STEP_ROWS = 8 };
+int aa_test_anderson_step(aa_ctx ctx, int m, long long na, long long nb, long long eff, const double* G, double* cur,
+                          double* dF, double* dG, int* ctl9, double* scale, double* M, double* coef, double* aa_s,
+                          const long long* mask4, int nblocks, int flags, double* red, long long red_cap, double* out,
+                          double* copy_to, int* info3);
 
 #ifdef __cplusplus
 }

@@ -5,11 +5,14 @@
 //   op 2: StVKTet prox (L-BFGS)         (TetEnergyTerm.cpp:151-162, 256-307)
 //   op 3: TriEnergyTerm::prox  H        (admm_anderson_hard_zxu/src/TriEnergyTerm.cpp:74-105)
 //   op 4: Eigen COD solve of a k x k normal-equation matrix (AndersonAcceleration.h:193-196)
+//   op 5: AndersonAcceleration itself: init(u0), then T times compute(G_k, u) (AndersonAcceleration.h:94-135)
 // input : int32 op, int32 count, then per case: double params[4], double in[K] (K = 9 tet, 6 tri,
-//         1+k*k+k for COD with k stored as params[0])
-// output: per case double out[9] (or k for COD)
+//         1+k*k+k for COD with k stored as params[0]; op 5: params = m, dim, eff, T, then u0[dim]
+//         and G[T][dim])
+// output: per case double out[9] (or k for COD; op 5: u[T][dim], the accelerated iterate of every call)
 #include "TetEnergyTerm.hpp"
 #include "TriEnergyTerm.hpp"
+#include "AndersonAcceleration.h"
 #include <Eigen/Dense>
 #include <cstdio>
 #include <cstdlib>
@@ -54,6 +57,17 @@ int main(int argc, char** argv) {
             Eigen::MatrixXd W = Eigen::MatrixXd::Identity(6, 6);
             t.prox(W, zi, vi);
             fwrite(zi.data(), 8, 6, o);
+        } else if (op == 5) {
+            const int m = (int)prm[0], dim = (int)prm[1], eff = (int)prm[2], T = (int)prm[3];
+            Eigen::VectorXd u(dim), g(dim);
+            if (fread(u.data(), 8, dim, f) != (size_t)dim) return 2;
+            AndersonAcceleration aa(m, dim, eff);
+            aa.init(u);
+            for (int k = 0; k < T; ++k) {
+                if (fread(g.data(), 8, dim, f) != (size_t)dim) return 2;
+                aa.compute(g, u);
+                fwrite(u.data(), 8, dim, o);
+            }
         } else {
             const int k = (int)prm[0];
             std::vector<double> M(k * k), b(k);

@@ -116,7 +116,7 @@ def case_names(extras=True):
     terms or wind (the oracle restates the core path only; those are pinned to the reference's
     own outputs directly)."""
     names = sorted(f[:-4] for f in os.listdir(GOLDEN)
-                   if f.endswith(".npz") and f not in ("elements.npz", "geom_elements.npz")
+                   if f.endswith(".npz") and f not in ("elements.npz", "geom_elements.npz", "anderson.npz")
                    and not f.startswith(("geom_", "full_", "mesh_", "eps_", "quality_")))
     if extras:
         return names
